@@ -1,7 +1,12 @@
 #!/usr/bin/env python3
 """bench.py — headline benchmark: PPO / CartPole-v1 at 4096 envs per GPU (BASELINE.json configs[1] / [4]).
 
-    python bench.py --gpus N --steps K --warmup W
+    python bench.py --gpus N --steps K --warmup W [--full] [--dump-outputs DIR]
+    A plain run does what the headline needs and nothing else: set-up, clock ramp, W warm-up updates, the K timed updates, the line.
+    --full adds everything measured beside the headline: two repeat windows and the all-launches-bracketed window, the per-kernel breakdown, the bf16x3 variant,
+        the sharded-route leg, the multi-rank collective diagnostics and carrier legs, the CPU baselines and the config3_* / config4_* workloads.
+    --dump-outputs DIR writes what the K-th timed update left for its caller (parameters, Adam moments, last gradient and loss terms, the rollout's storage)
+        as DIR/<name>.npy (float32 / float64, ~23 MB), rank 0 only; the same arguments give the same inputs in every run.
     N > 1 without WORLD_SIZE in the environment: this process — before it imports torch or touches a GPU — starts
         python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port <free> bench.py --gpus N ...
     as a CHILD process (never exec), relays rank 0's JSON line and exits with the child's return code.  Launched by the driver through
@@ -15,10 +20,10 @@ updates bracketed by barrier + torch.cuda.synchronize(); MAX over ranks; rank 0 
   roofline   = the dominant kernel (grad_kernel: f32 MFMA bound): algorithmic FLOPs per launch / its average launch
                duration, measured live over the timed region with HIP events on the launch stream (mi_prof_*).
   cpu_baseline = the CPU oracle (a C port of the reference loop, OpenMP over envs / rows) on this box's host cores,
-               rank 0 and N = 1 only, on a bounded sample of the SAME workload; cpu_baseline_n1 = the same oracle at the
+               --full, rank 0 and N = 1 only, on a bounded sample of the SAME workload; cpu_baseline_n1 = the same oracle at the
                reference's own shape (1 env, 1 thread), the like-for-like stand-in for the unmodified ppo.py.
 Inputs are resident in HBM when the timed region starts (storage, parameters and env state never leave the device).
-At N = 1 the same JSON line also carries `config3_dqn` and `config4_sac`: BASELINE.json configs[2] / [3] run AFTER (outside)
+With --full at N = 1 the same JSON line also carries `config3_dqn` and `config4_sac`: BASELINE.json configs[2] / [3] run AFTER (outside)
 the PPO timed region, each with its own ms_per_step, dominant-kernel roofline (HIP events) and oracle CPU baseline.
 """
 import argparse
@@ -849,15 +854,44 @@ def sharded_route_leg(eng, one_update, timed_updates, u0, steps, dev, base_ms, b
     return out
 
 
+DUMP_LIMIT_BYTES = 64 << 20
+
+
+def dump_outputs(path, eng, agent, opt, stats_host):
+    """--dump-outputs: what the last timed update handed its caller, one DIR/<name>.npy each (float32, or float64 where float32 would not hold the integers).
+    Called right behind the timed window, before anything else runs on the engine."""
+    import numpy as np
+    import torch
+
+    torch.cuda.synchronize()
+    f32 = lambda t: t.detach().cpu().numpy().astype(np.float32)   # noqa: E731
+    arrays = {
+        "params": f32(agent.flat), "adam_exp_avg": f32(opt.exp_avg), "adam_exp_avg_sq": f32(opt.exp_avg_sq), "grad_norm": f32(opt.grad_norm),
+        "grads": f32(eng.grads), "loss_terms": f32(eng.loss_terms),
+        "observations": f32(eng.observations), "actions": f32(eng.actions), "log_probs": f32(eng.log_probs), "rewards": f32(eng.rewards),
+        "dones": f32(eng.dones), "values": f32(eng.values), "advantages": f32(eng.advantages), "returns": f32(eng.returns),
+        "next_observation": f32(eng.observation),
+        "episode_summary": stats_host.numpy().astype(np.float64),
+    }
+    total = sum(a.nbytes for a in arrays.values())
+    assert total <= DUMP_LIMIT_BYTES, "outputs of %d bytes exceed the %d-byte limit" % (total, DUMP_LIMIT_BYTES)
+    os.makedirs(path, exist_ok=True)
+    for name, a in arrays.items():
+        np.save(os.path.join(path, name + ".npy"), a)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=50)
     ap.add_argument("--warmup", type=int, default=5)
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--headline-only", action="store_true", help="skip the config-3 (DQN) / config-4 (SAC) extra keys, the bf16x3 variant and the sharded-route leg")
-    ap.add_argument("--single-window", action="store_true", help="only the one timed window of K steps (no repeat windows)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baselines")
+    ap.add_argument("--headline-only", action="store_true", help="with --full: skip the config-3 (DQN) / config-4 (SAC) extra keys, the bf16x3 variant and the sharded-route leg")
+    ap.add_argument("--single-window", action="store_true", help="with --full: only the one timed window of K steps (no repeat windows)")
     ap.add_argument("--no-prewarm", action="store_true", help="skip the clock ramp (PREWARM_UPDATES throwaway updates on a scratch engine before the W warm-up steps)")
+    ap.add_argument("--full", action="store_true", help="also run everything measured beside the headline (repeat windows, breakdown, variant, legs, collectives, "
+                                                        "CPU baselines, config3/config4); without it only the headline window runs")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None, help="write the last timed update's outputs as DIR/<name>.npy (rank 0)")
     args = ap.parse_args()
 
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
@@ -1011,9 +1045,12 @@ def main():
     for u in range(args.warmup):
         one_update(u)
     dt, prof = timed_updates(args.warmup, args.steps)   # THE measurement: f32 contractions
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, eng, agent, opt, stats_host)
+    # everything from here to the line is --full only
     # two more windows of the same K updates right behind it: the spread says whether a margin of a fraction of a per cent is signal
     windows = [dt]
-    if not args.single_window:
+    if args.full and not args.single_window:
         for _ in range(2):
             windows.append(timed_updates(num_updates, args.steps)[0])
 
@@ -1022,7 +1059,7 @@ def main():
     # a sharded headline is only worth its number if the exchange really happened: right behind the timed windows, no wait of the carrier may have run out on any rank
     # and the replicas must still be bitwise identical (one MAX all-reduce of a checksum; host-synchronising, outside the timed region)
     headline_exchange = None
-    if world > 1:
+    if args.full and world > 1:
         try:
             eng.check_replicas()
             headline_exchange = {"replicas_identical": True}
@@ -1032,7 +1069,7 @@ def main():
     # BESIDE the headline, never instead of it: the same three windows on libmirl's P2P carrier (rank-ordered sum over hipIpc-mapped inboxes, the gradient exchange
     # inside the slab-sum launch), the engine simply going on learning; then back to the headline's carrier for everything behind
     p2p_beside = None
-    if policy_on and headline_carrier == "rccl" and carriers.get("p2p", (None,))[0] is not None and os.environ.get("MIRL_BENCH_P2P_BESIDE", "1") != "0":
+    if args.full and policy_on and headline_carrier == "rccl" and carriers.get("p2p", (None,))[0] is not None and os.environ.get("MIRL_BENCH_P2P_BESIDE", "1") != "0":
         p2p_beside = {}
         try:
             DD.use_comm(carriers["p2p"][0])
@@ -1055,12 +1092,12 @@ def main():
 
     # the round-1..3 methodology beside it: one more window with a pair of HIP events around EVERY gradient launch of EVERY update
     dt_all = None
-    if not args.single_window:
+    if args.full and not args.single_window:
         dt_all = timed_updates(num_updates, args.steps, prof_every=1)[0]
 
     # beside it, never instead of it: the same K updates with the split-bf16 experiment switched on (include/mi_rl.h, mi_ppo_set_contraction)
     variant = None
-    if not args.headline_only:
+    if args.full and not args.headline_only:
         D.set_contraction("bf16x3")
         for u in range(2):
             one_update(num_updates - 1)
@@ -1070,14 +1107,16 @@ def main():
 
     # untimed: per-kernel breakdown of 3 more updates (all tags)
     n_break = 3
-    N.prof_begin(n_break * 64 + 64)
-    for u in range(n_break):
-        eng.update()
-    breakdown = N.prof_end()
+    breakdown = None
+    if args.full:
+        N.prof_begin(n_break * 64 + 64)
+        for u in range(n_break):
+            eng.update()
+        breakdown = N.prof_end()
 
     sharded = None
-    leg = os.environ.get("MIRL_BENCH_SHARDED_LEG", "")   # "1": also with --headline-only (A/B builds); "0": never
-    if world == 1 and leg != "0" and (not args.headline_only or leg == "1"):
+    leg = os.environ.get("MIRL_BENCH_SHARDED_LEG", "")   # "1": also with --full --headline-only (A/B builds); "0": never
+    if args.full and world == 1 and leg != "0" and (not args.headline_only or leg == "1"):
         try:
             sharded = sharded_route_leg(eng, one_update, timed_updates, num_updates - 1, args.steps, dev, 1e3 * dt / args.steps,
                                         1e3 * prof["grad"][0] / max(prof["grad"][1], 1))
@@ -1090,7 +1129,7 @@ def main():
     comm = _dist.native_comm(eng.pg) if dist_on else None
     eng_native = comm is not None
     collectives = None
-    if dist_on:   # every rank takes part in the collectives; a failure here must not cost the measurement above its line
+    if args.full and dist_on:   # every rank takes part in the collectives; a failure here must not cost the measurement above its line
         try:
             collectives = collective_diagnostics(eng, comm, world, dev, breakdown, n_break)
         except Exception as ex:  # noqa: BLE001
@@ -1139,9 +1178,6 @@ def main():
             "hbm_roofline": {"algorithmic_bytes_per_env_step": BYTES_PER_ENV_STEP,
                              "achieved_GBps_per_gpu": round(BYTES_PER_ENV_STEP * steps_per_s / world / 1e9, 2), "peak_GBps": PEAK_HBM_GBS,
                              "frac": round(BYTES_PER_ENV_STEP * steps_per_s / world / 1e9 / PEAK_HBM_GBS, 6)},
-            "kernel_ms_per_update_bracketed": dict({k: round(v[0] / n_break, 4) for k, v in breakdown.items() if v[1]},
-                                                   note="HIP events around EVERY tagged launch in an untimed pass of %d updates: each figure carries its own event overhead "
-                                                        "(~3 us per launch); the sum exceeds the timed window by construction — use kernel_device_ms_per_update for a sum" % n_break),
             "kernel_device_ms_per_update": kernel_device_durations(1e3 * dt / args.steps),
             "methodology": {"prewarm_updates": prewarm_updates, "events": "HIP events around grad_kernel's 16 launches of every %d-th update of the timed windows" % PROF_EVERY,
                             "protocol_changed_in": "r04 (rounds 1-3: no prewarm, events around every launch of every update; BASELINE.md section 3 names neither)",
@@ -1158,6 +1194,11 @@ def main():
                                                              "not idle between the ramp and the warm-up); the W warm-up and K timed updates are the measured engine's first W + K updates; "
                                                              "--no-prewarm turns it off"},
         }
+        if breakdown is not None:
+            out["kernel_ms_per_update_bracketed"] = dict({k: round(v[0] / n_break, 4) for k, v in breakdown.items() if v[1]},
+                                                         note="HIP events around EVERY tagged launch in an untimed pass of %d updates: each figure carries its own event "
+                                                              "overhead (~3 us per launch); the sum exceeds the timed window by construction — use "
+                                                              "kernel_device_ms_per_update for a sum" % n_break)
         wms = sorted(1e3 * w / args.steps for w in windows)
         out["timed_windows"] = {"count": len(wms), "steps_each": args.steps, "ms_per_step": [round(1e3 * w / args.steps, 4) for w in windows],
                                 "min": round(wms[0], 4), "median": round(wms[len(wms) // 2], 4), "max": round(wms[-1], 4),
@@ -1203,10 +1244,10 @@ def main():
                 "achieved_algorithmic": round(flops_per_launch / (v_us * 1e-6) / 1e12, 2) if vg_n else 0.0,
                 "frac_algorithmic": round(flops_per_launch / (v_us * 1e-6) / 1e12 / PEAK_BF16_MFMA_TFLOPS, 4) if vg_n else 0.0,
                 "note": "VALU-issue- and dependency-bound (176 of ~550 vector instructions per tile are the operand splits), not matrix-bound: docs/LEDGER.md"}
-        if world == 1 and not args.no_cpu_baseline:
+        if args.full and world == 1 and not args.no_cpu_baseline:
             out["cpu_baseline"] = cpu_baseline(params0, float(os.environ.get("MIRL_CPU_BASELINE_SECONDS", "10")))  # bounded sample (default 10 s)
             out["cpu_baseline_n1"] = cpu_baseline_n1(params0)
-        if world == 1 and not args.headline_only:
+        if args.full and world == 1 and not args.headline_only:
             cs = 0.0 if args.no_cpu_baseline else 3.0
             del eng, env, agent, opt
             out["config3_dqn"] = bench_dqn(dev, cpu_seconds=cs)

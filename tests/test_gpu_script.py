@@ -136,7 +136,7 @@ def test_bench_contract_line():
 
     if not torch.cuda.is_available():
         pytest.skip("needs an MI355X")
-    out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "3", "--warmup", "1"], env=dict(os.environ, PYTHONPATH=ROOT, MIRL_CPU_BASELINE_SECONDS="1"),
+    out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "3", "--warmup", "1", "--full"], env=dict(os.environ, PYTHONPATH=ROOT, MIRL_CPU_BASELINE_SECONDS="1"),
                          capture_output=True, text=True, timeout=900, cwd=ROOT)
     assert out.returncode == 0, out.stderr[-3000:]
     lines = [ln for ln in out.stdout.splitlines() if ln.startswith("{")]
@@ -184,6 +184,43 @@ def test_bench_contract_line():
         assert d[key]["ms_per_step"] > 0 and 0.2 < d[key]["frac_of_chain_floor"] < 1.0, d[key]
 
 
+def test_bench_plain_line_and_dumped_outputs(tmp_path):
+    """A plain bench.py run (no --full) times the headline window only and prints the same contract keys; --dump-outputs writes the last timed update's outputs as
+    float .npy files (<= 64 MB), and two runs with the same arguments write the same arrays."""
+    import json
+    import torch
+
+    if not torch.cuda.is_available():
+        pytest.skip("needs an MI355X")
+    lines, dirs = [], []
+    for i in range(2):
+        d = str(tmp_path / ("run%d" % i))
+        out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "3", "--warmup", "1", "--dump-outputs", d], env=dict(os.environ, PYTHONPATH=ROOT),
+                             capture_output=True, text=True, timeout=600, cwd=ROOT)
+        assert out.returncode == 0, out.stderr[-3000:]
+        assert len(out.stdout.splitlines()) == 1, out.stdout[-2000:]
+        lines.append(json.loads(out.stdout))
+        dirs.append(d)
+    d = lines[0]
+    for k in ("metric", "value", "unit", "higher_is_better", "dtype", "ms_per_step", "roofline"):
+        assert k in d, k
+    assert d["steps"] == 3 and d["warmup"] == 1 and d["unit"] == "env-steps/s" and d["higher_is_better"] is True and d["dtype"] == "f32" and d["params_finite"] is True
+    assert abs(d["value"] - 3 * 128 * 4096 / (3 * d["ms_per_step"] * 1e-3)) < 1e-3 * d["value"]
+    assert d["timed_windows"]["count"] == 1 and d["timed_windows"]["ms_per_step"][0] == d["ms_per_step"]
+    for k in ("cpu_baseline", "cpu_baseline_n1", "config3_dqn", "config4_sac", "variant_bf16x3", "sharded_route", "kernel_ms_per_update_bracketed"):
+        assert k not in d, k                                      # --full only
+    names = sorted(f for f in os.listdir(dirs[0]) if f.endswith(".npy"))
+    assert names == sorted(os.listdir(dirs[1])) and "params.npy" in names and "observations.npy" in names
+    total = 0
+    for f in names:
+        a, b = np.load(os.path.join(dirs[0], f)), np.load(os.path.join(dirs[1], f))
+        assert a.dtype in (np.float32, np.float64) and a.dtype == b.dtype and a.shape == b.shape, f
+        assert np.array_equal(a, b, equal_nan=True), f
+        total += a.nbytes
+    assert total <= 64 << 20
+    assert np.load(os.path.join(dirs[0], "params.npy")).shape == (9155,) and np.load(os.path.join(dirs[0], "observations.npy")).shape == (129, 4096, 4)
+
+
 @pytest.mark.parametrize("mirl_comm", [None, "rccl"])
 def test_bench_two_ranks_code_path_on_one_gpu(mirl_comm):
     """`python bench.py --gpus 2` as the driver types it: the parent (no GPU call, no torch import) starts the two ranks through torch.distributed.run as a
@@ -201,7 +238,7 @@ def test_bench_two_ranks_code_path_on_one_gpu(mirl_comm):
     env.pop("WORLD_SIZE", None); env.pop("RANK", None); env.pop("MIRL_COMM", None)
     if mirl_comm:
         env["MIRL_COMM"] = mirl_comm
-    out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "2", "--warmup", "1"], env=env, capture_output=True, text=True,
+    out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "2", "--warmup", "1", "--full"], env=env, capture_output=True, text=True,
                          timeout=900, cwd=ROOT)
     assert out.returncode == 0, out.stderr[-3000:]
     lines = out.stdout.splitlines()
@@ -239,7 +276,7 @@ def test_bench_native_rccl_diagnostics_at_world_size_1():
 
     if not torch.cuda.is_available():
         pytest.skip("needs an MI355X")
-    out = run_with_port(lambda port: ([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "2", "--warmup", "1", "--headline-only", "--no-cpu-baseline"],
+    out = run_with_port(lambda port: ([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "2", "--warmup", "1", "--headline-only", "--no-cpu-baseline", "--full"],
                                       dict(os.environ, PYTHONPATH=ROOT, MIRL_FORCE_PG="1", MASTER_ADDR="127.0.0.1", MASTER_PORT=str(port), RANK="0", WORLD_SIZE="1", LOCAL_RANK="0",
                                            HSA_ENABLE_IPC_MODE_LEGACY="0")), capture_output=True, text=True, timeout=600, cwd=ROOT)
     assert out.returncode == 0, out.stderr[-3000:]
@@ -275,7 +312,7 @@ def test_bench_started_as_ranks_by_torch_distributed_run():
     for k in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MIRL_COMM", "HSA_ENABLE_IPC_MODE_LEGACY"):
         env.pop(k, None)
     out = run_with_port(lambda port: ([sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2", "--master-addr", "127.0.0.1", "--master-port", str(port),
-                                       os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "2", "--warmup", "1", "--headline-only"], env), capture_output=True, text=True,
+                                       os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "2", "--warmup", "1", "--headline-only", "--full"], env), capture_output=True, text=True,
                         timeout=900, cwd=ROOT)
     assert out.returncode == 0, out.stderr[-3000:]
     lines = [ln for ln in out.stdout.splitlines() if ln.startswith('{"metric"')]
@@ -297,7 +334,7 @@ def test_bench_auto_carrier_tunes_on_real_updates_at_world_size_1():
 
     if not torch.cuda.is_available():
         pytest.skip("needs an MI355X")
-    out = run_with_port(lambda port: ([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "2", "--warmup", "1", "--headline-only", "--no-cpu-baseline"],
+    out = run_with_port(lambda port: ([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "2", "--warmup", "1", "--headline-only", "--no-cpu-baseline", "--full"],
                                       dict(os.environ, PYTHONPATH=ROOT, MIRL_FORCE_PG="1", MIRL_COMM="auto", MIRL_BENCH_CARRIER_LEGS="0", MASTER_ADDR="127.0.0.1", MASTER_PORT=str(port),
                                            RANK="0", WORLD_SIZE="1", LOCAL_RANK="0", HSA_ENABLE_IPC_MODE_LEGACY="0")), capture_output=True, text=True, timeout=600, cwd=ROOT)
     assert out.returncode == 0, out.stderr[-3000:]
@@ -331,7 +368,7 @@ def test_two_gpus_bench_headline_runs_on_rccl_with_p2p_beside_it():
     env = dict(os.environ, PYTHONPATH=ROOT)
     for k in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MIRL_COMM", "MIRL_BENCH_BACKEND", "MIRL_BENCH_ONE_GPU"):
         env.pop(k, None)
-    out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "5", "--warmup", "2", "--headline-only"], env=env, capture_output=True,
+    out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "5", "--warmup", "2", "--headline-only", "--full"], env=env, capture_output=True,
                          text=True, timeout=900, cwd=ROOT)
     assert out.returncode == 0, out.stderr[-3000:]
     lines = out.stdout.splitlines()

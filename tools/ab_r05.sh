@@ -5,7 +5,8 @@
 # then on the GPU box: tools/ab_r05.sh   (profiles/r06d_ab_against_r05_tree.txt)
 for r in 1 2 3 4 5; do
   for t in ab_r05 .; do
-    b=$(cd $t && MIRL_BENCH_SHARDED_LEG=1 PYTHONPATH=$(pwd) timeout 300 python bench.py --steps 20 --warmup 5 --no-cpu-baseline --headline-only 2>/dev/null | grep '^{"metric"' | python -c "
+    FULL=$([ "$t" = . ] && echo --full)   # the round-5 tree's bench.py has no --full: everything ran by default there
+    b=$(cd $t && MIRL_BENCH_SHARDED_LEG=1 PYTHONPATH=$(pwd) timeout 300 python bench.py --steps 20 --warmup 5 --no-cpu-baseline --headline-only $FULL 2>/dev/null | grep '^{"metric"' | python -c "
 import sys, json
 d = json.loads(sys.stdin.readline())
 s = d['sharded_route']

@@ -6,7 +6,7 @@ STEPS=$1; REPS=$2; shift; shift
 for r in $(seq 1 $REPS); do
   for so in "$@"; do
     export MIRL_SO=$(pwd)/$so
-    b=$(MIRL_BENCH_SHARDED_LEG=1 timeout 300 python bench.py --steps $STEPS --warmup 5 --no-cpu-baseline --headline-only 2>/dev/null | grep '^{"metric"' | python -c "
+    b=$(MIRL_BENCH_SHARDED_LEG=1 timeout 300 python bench.py --steps $STEPS --warmup 5 --no-cpu-baseline --headline-only --full 2>/dev/null | grep '^{"metric"' | python -c "
 import sys, json
 d = json.loads(sys.stdin.readline())
 s = d['sharded_route']
