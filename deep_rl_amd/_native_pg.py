@@ -1,0 +1,76 @@
+"""ctypes binding of libmirl_pg.so — the C ABI declared in include/mi_reinforce.h (REINFORCE on CartPole-v1).
+
+A second library beside libmirl.so.  It is loaded LAZILY, on the first ``lib()`` call: importing ``deep_rl_amd`` works with only libmirl.so present, and the first
+use of the REINFORCE engine without a built ``deep_rl_amd/libmirl_pg.so`` raises ``MiError`` — there is no fallback.  Build both with ``make -C deep_rl_amd/csrc``.
+"""
+import ctypes as C
+import os
+
+from ._native import MiError, ptr, stream_ptr  # noqa: F401  (re-exported for the engine)
+
+_HERE = os.path.dirname(os.path.abspath(__file__))
+SO_PATH = os.environ.get("MIRL_PG_SO", os.path.join(_HERE, "libmirl_pg.so"))  # MIRL_PG_SO: A/B and diagnostic builds of the same ABI
+
+ABI_VERSION = 1   # == MI_PG_VERSION of the include/mi_reinforce.h these signatures and struct layouts were written against
+NPARAMS = 898
+HID = 128
+MAX_STEPS = 500
+ROWS = 501
+STREAM_DROPOUT = 8
+KEEP_BELOW = 0x66666666
+MI_PG_OK = 0
+
+
+class PGBuffers(C.Structure):   # mi_pg_buffers_t
+    _fields_ = [(n, C.c_void_p) for n in (
+        "params", "exp_avg", "exp_avg_sq", "grads", "observations", "actions", "log_probs", "returns", "b_returns", "mask_bits", "lengths", "ep_returns",
+        "workspace", "forced_reset", "forced_actions", "forced_masks")]
+
+
+class PGHparams(C.Structure):   # mi_pg_hparams_t
+    _fields_ = [("gamma", C.c_float), ("reserved", C.c_int32), ("opt_step", C.c_int64), ("lr", C.c_double), ("beta1", C.c_double), ("beta2", C.c_double),
+                ("eps", C.c_double)]
+
+
+_VP, _I, _F, _D, _I64, _SZ = C.c_void_p, C.c_int, C.c_float, C.c_double, C.c_int64, C.c_size_t
+SIGNATURES = {
+    "mi_pg_version": (_I, []),
+    "mi_pg_last_error": (C.c_char_p, []),
+    "mi_pg_source_id": (C.c_char_p, []),
+    "mi_pg_workspace_bytes": (_SZ, [_I]),
+    "mi_pg_forward": (_I, [_VP, _VP, _I, _VP, _VP, _VP]),
+    "mi_pg_rollout_episodes": (_I, [_VP, C.POINTER(PGBuffers), _VP]),
+    "mi_pg_returns": (_I, [C.POINTER(PGBuffers), _I, _F, _VP]),
+    "mi_pg_grad": (_I, [C.POINTER(PGBuffers), _I, _VP]),
+    "mi_pg_adam": (_I, [_VP] * 4 + [_I, _I64, _D, _D, _D, _D, _VP]),
+    "mi_pg_update": (_I, [_VP, C.POINTER(PGBuffers), C.POINTER(PGHparams), _VP]),
+}
+
+_lib = None
+
+
+def lib():
+    """Load libmirl_pg.so (once, on first use).  Fails loudly: the HIP library is not optional for the REINFORCE path."""
+    global _lib
+    if _lib is None:
+        if not os.path.exists(SO_PATH):
+            raise MiError("deep_rl_amd: %s is missing — build it with `make -C deep_rl_amd/csrc` (hipcc --offload-arch=gfx950); there is no CPU fallback" % SO_PATH)
+        L = C.CDLL(SO_PATH)
+        for name, (res, args) in SIGNATURES.items():
+            fn = getattr(L, name)
+            fn.restype, fn.argtypes = res, args
+        got = L.mi_pg_version()
+        if got != ABI_VERSION:
+            raise MiError("deep_rl_amd: %s reports ABI version %d, this binding is written against %d — rebuild it (make -C deep_rl_amd/csrc)" % (SO_PATH, got, ABI_VERSION))
+        _lib = L
+    return _lib
+
+
+def check(rc, what=""):
+    if rc != MI_PG_OK:
+        msg = lib().mi_pg_last_error()
+        raise MiError("%s failed (rc=%d): %s" % (what or "libmirl_pg call", rc, msg.decode() if msg else "?"))
+
+
+def source_id():
+    return lib().mi_pg_source_id().decode()

@@ -258,3 +258,30 @@ class DuelingQNetwork(_FlatModule):
         q = torch.empty((obs.shape[0], 2), dtype=torch.float32, device=self.device)
         N.check(N.lib().mi_dqn_forward(N.ptr(self.eff), N.ptr(obs), obs.shape[0], N.ptr(q), N.stream_ptr(self.device)), "mi_dqn_forward")
         return q.reshape(*lead, 2)
+
+
+class DropoutPolicy(_FlatModule):
+    """The policy of the reference reinforce.py:40-46 (4 -> 128, Dropout(p=0.6), ReLU, 128 -> 2, Softmax; torch default init) over one flat fp32 device
+    buffer of 898 floats (include/mi_reinforce.h: W1 128x4, b1 128, W2 2x128, b2 2 — the order of ``agent.parameters()``).  The layer list is the
+    reference's, so ``torch.manual_seed(s)`` before construction gives its initial weights.  Acting with live dropout, as the reference does (it never
+    calls ``.eval()``), happens inside ReinforceEngine's episode kernel with a keyed mask stream; ``forward`` here evaluates given rows."""
+
+    def __init__(self, env, device=None):
+        super().__init__()
+        from . import _native_pg as PG
+        obs_dim = int(np.prod(env.observation_space.shape))
+        if obs_dim != 4 or env.action_space.n != 2:
+            raise N.MiError("the HIP kernels are specialised for CartPole (obs 4, actions 2)")
+        self.network = nn.Sequential(nn.Linear(obs_dim, 128), nn.Dropout(p=0.6), nn.ReLU(), nn.Linear(128, env.action_space.n), nn.Softmax(-1))
+        self._finish(env, device, PG.NPARAMS)
+
+    def forward(self, observation, mask_bits=None):
+        """-> action probabilities.  mask_bits (rows, 4) int32 / uint32: the 128 keep bits of each row (training mode); None: eval mode (no dropout)."""
+        from . import _native_pg as PG
+        obs = observation.to(self.device, torch.float32)
+        lead = obs.shape[:-1]
+        obs = obs.reshape(-1, 4).contiguous()
+        mb = None if mask_bits is None else mask_bits.to(self.device).reshape(-1, 4).contiguous()
+        probs = torch.empty((obs.shape[0], 2), dtype=torch.float32, device=self.device)
+        PG.check(PG.lib().mi_pg_forward(N.ptr(self.flat), N.ptr(obs), obs.shape[0], N.ptr(mb), N.ptr(probs), N.stream_ptr(self.device)), "mi_pg_forward")
+        return probs.reshape(*lead, 2)

@@ -12,6 +12,7 @@ import torch
 from . import _native as N
 from .dqn_engine import DQNEngine, DuelingDQNEngine, PERDQNEngine
 from .engine import PPOEngine
+from .reinforce_engine import ReinforceEngine
 from .sac_engine import SACEngine
 
 FORMAT = 1
@@ -45,7 +46,7 @@ def state_dict(engine, include_replay=True):
     env = engine.env
     st = {"format": np.int64(FORMAT), "kind": type(engine).__name__, "num_envs": np.int64(env.num_envs), "seed": np.int64(env._seed),
           "env_id_base": np.int64(env.env_id_base), "env_blob": _env_blob(env), "observation": engine.observation}
-    if isinstance(engine, PPOEngine):
+    if isinstance(engine, (PPOEngine, ReinforceEngine)):   # REINFORCE keeps nothing across updates but the env counters, the parameters and Adam's state
         st.update(params=engine.agent.flat, update_index=np.int64(engine.update_index), **_opt_state(engine.optimizer, "opt_"))
     elif isinstance(engine, DQNEngine):
         st.update(params=engine.q.flat, target=engine.target.flat, global_step=np.int64(engine.global_step), update_index=np.int64(engine.update_index),
@@ -103,7 +104,7 @@ def load(path, engine):
     dev = engine.device
     t = lambda name: torch.from_numpy(z[name]).to(dev)   # noqa: E731
     _env_restore(env, z["env_blob"])
-    if isinstance(engine, PPOEngine):
+    if isinstance(engine, (PPOEngine, ReinforceEngine)):
         _check_shape(z, "params", engine.agent.flat.shape)
     elif isinstance(engine, DQNEngine):
         _check_shape(z, "params", engine.q.flat.shape); _check_shape(z, "target", engine.target.flat.shape)
@@ -113,7 +114,7 @@ def load(path, engine):
         if name in z and hasattr(engine, name):
             _check_shape(z, name, getattr(engine, name).shape)
     engine.observation = t("observation")
-    if isinstance(engine, PPOEngine):
+    if isinstance(engine, (PPOEngine, ReinforceEngine)):
         engine.agent.flat.copy_(t("params")); engine.update_index = int(z["update_index"]); _opt_restore(engine.optimizer, z, "opt_")
     elif isinstance(engine, DQNEngine):
         engine.q.flat.copy_(t("params")); engine.target.flat.copy_(t("target"))
