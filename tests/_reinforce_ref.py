@@ -114,6 +114,39 @@ def returns_normalised(length, gamma=0.99):
         return Rr, ((Rr - mean) / denom).astype(f32)
 
 
+def forward64(params, X, M=None):
+    """float64 form of `forward` on the same f32 inputs: -> probs (rows, 2), log_probs (rows, 2), logits (rows, 2), Z (rows, 128) the hidden pre-activations"""
+    W1, b1, W2, b2 = [w.astype(np.float64) for w in unpack(params)]
+    X = np.asarray(X, np.float64).reshape(-1, 4)
+    Z = X @ W1.T + b1
+    H = np.maximum(Z, 0.0) if M is None else np.where(M, np.maximum(Z * 2.5, 0.0), 0.0)
+    L = H @ W2.T + b2
+    d = L - L.max(axis=1, keepdims=True)
+    lp = d - np.log(np.exp(d).sum(axis=1, keepdims=True))
+    return np.exp(lp), lp, L, Z
+
+
+def returns_normalised64(length, gamma=0.99):
+    """float64 form of `returns_normalised` (gamma is the f32 value the kernel is handed): -> (R, Rn); a one-row episode gives NaN in Rn"""
+    g = float(f32(gamma))
+    Rr = np.zeros(length, np.float64)
+    acc = 0.0
+    for t in range(length - 1, -1, -1):
+        acc = g * acc + 1.0; Rr[t] = acc
+    with np.errstate(invalid="ignore", divide="ignore"):
+        mean = Rr.sum() / np.float64(length)
+        var = ((Rr - mean) ** 2).sum() / np.float64(length - 1)
+        return Rr, (Rr - mean) / (np.sqrt(var) + np.exp(-5.0))
+
+
+def adam_step64(p, g, m, v, step, lr=1e-2, beta1=0.9, beta2=0.999, eps=1e-8):
+    """float64 form of `adam_step` (in place on float64 p, m, v)"""
+    g = np.asarray(g, np.float64)
+    m[:] = m + (1.0 - beta1) * (g - m)
+    v[:] = v * beta2 + (1.0 - beta2) * (g * g)
+    p[:] = p - (lr / (1.0 - beta1 ** step)) * (m / (np.sqrt(v) / np.sqrt(1.0 - beta2 ** step) + eps))
+
+
 def grad(params, X, A, M, Rn, dtype=f32):
     """gradient of sum(-log_prob * Rn) w.r.t. the flat parameters; dtype f32 (vectorised, numpy's own summation order) or f64"""
     W1, b1, W2, b2 = [w.astype(dtype) for w in unpack(params)]
