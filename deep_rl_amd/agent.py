@@ -285,3 +285,41 @@ class DropoutPolicy(_FlatModule):
         probs = torch.empty((obs.shape[0], 2), dtype=torch.float32, device=self.device)
         PG.check(PG.lib().mi_pg_forward(N.ptr(self.flat), N.ptr(obs), obs.shape[0], N.ptr(mb), N.ptr(probs), N.stream_ptr(self.device)), "mi_pg_forward")
         return probs.reshape(*lead, 2)
+
+
+class C51QNetwork(_FlatModule):
+    """QNetwork of the reference c51.py:24-37 (4 -> 120 -> 84 -> n_actions * n_atoms, ReLU, Unflatten, torch default init) over one flat fp32 device buffer of
+    27,934 floats (include/mi_c51.h).  The layer list is the reference's, so ``torch.manual_seed(s)`` before construction gives its initial weights.  The kernels
+    are specialised for CartPole and the reference's 101 atoms on [-100, 100]."""
+
+    def __init__(self, env, n_atoms=101, device=None):
+        super().__init__()
+        from . import _native_c51 as K
+        obs_dim = int(np.prod(env.observation_space.shape))
+        if obs_dim != 4 or getattr(env.action_space, "n", None) != 2:
+            raise N.MiError("the HIP kernels are specialised for CartPole (obs 4, actions 2)")
+        if int(n_atoms) != K.N_ATOMS:
+            raise N.MiError("the C51 kernels are specialised for n_atoms = %d (v_min = -100, v_max = 100); got %r" % (K.N_ATOMS, n_atoms))
+        self.network = nn.Sequential(nn.Linear(obs_dim, 120), nn.ReLU(), nn.Linear(120, 84), nn.ReLU(), nn.Linear(84, env.action_space.n * n_atoms),
+                                     nn.Unflatten(-1, (env.action_space.n, n_atoms)))
+        self.n_atoms = int(n_atoms)
+        self._finish(env, device, K.NPARAMS)
+
+    def _run(self, observation, want_probs, want_q):
+        from . import _native_c51 as K
+        obs = observation.to(self.device, torch.float32)
+        lead = obs.shape[:-1]
+        obs = obs.reshape(-1, 4).contiguous()
+        n = obs.shape[0]
+        probs = torch.empty((n, 2, K.N_ATOMS), dtype=torch.float32, device=self.device) if want_probs else None
+        q = torch.empty((n, 2), dtype=torch.float32, device=self.device) if want_q else None
+        K.check(K.lib().mi_c51_forward(N.ptr(self.flat), N.ptr(obs), n, N.ptr(probs), N.ptr(q), N.stream_ptr(self.device)), "mi_c51_forward")
+        return (probs.reshape(*lead, 2, K.N_ATOMS) if want_probs else None), (q.reshape(*lead, 2) if want_q else None)
+
+    def get_probs(self, observation):
+        """c51.py:36-37."""
+        return self._run(observation, True, False)[0]
+
+    def get_q_values(self, observation):
+        """torch.sum(get_probs(observation) * atoms, dim=-1) (c51.py:99) in the kernels' summation order."""
+        return self._run(observation, False, True)[1]

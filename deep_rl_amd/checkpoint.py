@@ -10,6 +10,7 @@ import numpy as np
 import torch
 
 from . import _native as N
+from .c51_engine import C51Engine
 from .dqn_engine import DQNEngine, DuelingDQNEngine, PERDQNEngine
 from .engine import PPOEngine
 from .reinforce_engine import ReinforceEngine
@@ -41,6 +42,11 @@ def _opt_restore(o, z, prefix):
     o.step_count = int(z[prefix + "step_count"]); o.param_groups[0]["lr"] = float(z[prefix + "lr"])
 
 
+def _target_net(engine):
+    """the target network of an off-policy engine (C51Engine's `target` is its method for the projected targets)"""
+    return engine.target_network if isinstance(engine, C51Engine) else engine.target
+
+
 def state_dict(engine, include_replay=True):
     """-> {name: array}: everything needed to continue `engine` exactly."""
     env = engine.env
@@ -48,8 +54,8 @@ def state_dict(engine, include_replay=True):
           "env_id_base": np.int64(env.env_id_base), "env_blob": _env_blob(env), "observation": engine.observation}
     if isinstance(engine, (PPOEngine, ReinforceEngine)):   # REINFORCE keeps nothing across updates but the env counters, the parameters and Adam's state
         st.update(params=engine.agent.flat, update_index=np.int64(engine.update_index), **_opt_state(engine.optimizer, "opt_"))
-    elif isinstance(engine, DQNEngine):
-        st.update(params=engine.q.flat, target=engine.target.flat, global_step=np.int64(engine.global_step), update_index=np.int64(engine.update_index),
+    elif isinstance(engine, (DQNEngine, C51Engine)):   # C51: the same ring, two networks, one Adam
+        st.update(params=engine.q.flat, target=_target_net(engine).flat, global_step=np.int64(engine.global_step), update_index=np.int64(engine.update_index),
                   **_opt_state(engine.optimizer, "opt_"))
         if isinstance(engine, PERDQNEngine):
             st.update(max_priority=engine.max_priority)
@@ -106,8 +112,8 @@ def load(path, engine):
     _env_restore(env, z["env_blob"])
     if isinstance(engine, (PPOEngine, ReinforceEngine)):
         _check_shape(z, "params", engine.agent.flat.shape)
-    elif isinstance(engine, DQNEngine):
-        _check_shape(z, "params", engine.q.flat.shape); _check_shape(z, "target", engine.target.flat.shape)
+    elif isinstance(engine, (DQNEngine, C51Engine)):
+        _check_shape(z, "params", engine.q.flat.shape); _check_shape(z, "target", _target_net(engine).flat.shape)
     else:
         _check_shape(z, "actor", engine.actor.flat.shape); _check_shape(z, "q", engine.q_flat.shape); _check_shape(z, "q_target", engine.qt_flat.shape)
     for name in ("observations", "actions", "rewards", "terminated", "priorities"):
@@ -116,8 +122,8 @@ def load(path, engine):
     engine.observation = t("observation")
     if isinstance(engine, (PPOEngine, ReinforceEngine)):
         engine.agent.flat.copy_(t("params")); engine.update_index = int(z["update_index"]); _opt_restore(engine.optimizer, z, "opt_")
-    elif isinstance(engine, DQNEngine):
-        engine.q.flat.copy_(t("params")); engine.target.flat.copy_(t("target"))
+    elif isinstance(engine, (DQNEngine, C51Engine)):
+        engine.q.flat.copy_(t("params")); _target_net(engine).flat.copy_(t("target"))
         if isinstance(engine, DuelingDQNEngine):
             engine.q.repack(); engine.target.repack()
         engine.global_step, engine.update_index = int(z["global_step"]), int(z["update_index"])

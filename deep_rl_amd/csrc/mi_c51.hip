@@ -1,0 +1,619 @@
+// mi_c51.hip — libmirl_c51.so: C51 categorical DQN on CartPole-v1 (reference c51.py) for gfx950.  C ABI, numerics and RNG contract: include/mi_c51.h.
+//
+// One 256-thread workgroup evaluates one network row at a time with the WHOLE network in its registers (112 KB: thread r < 202 holds row r of W3, thread c * 84 + o a
+// 40-wide third of row o of W2, thread u < 120 row u of W1), loaded once per launch and kept across everything the workgroup does:
+//   c51_act_kernel      a workgroup walks its envs (n = g, g + G, ...), each through all steps of the chunk: weights resident across the steps, fp64 physics in every
+//                       thread (same cost as in one), exploring steps skip the forward.
+//   c51_grad_kernel     a workgroup walks its batch rows twice: with the TARGET network it writes next_actions / target_probs (softmax, greedy action, categorical
+//                       projection per target atom), then with the ONLINE network forward + backward of the same rows into register accumulators — one slab per workgroup.
+//   c51_reduce_kernel   fixed-order slab sum (+ Adam).
+// All arithmetic on the VALU in fp32 with the summation orders of the header; no floating-point atomics.
+// Uses mi_common.h read-only for the device helpers; none of its host-side macros (they call into libmirl.so).
+#include "mi_common.h"
+
+#include "../../include/mi_c51.h"
+
+#include <stdarg.h>
+
+#define C5_H1 MI_C51_H1
+#define C5_H2 MI_C51_H2
+#define C5_NA MI_C51_N_ATOMS
+#define C5_NL (2 * MI_C51_N_ATOMS)
+#define C5_W1 MI_C51_W1
+#define C5_B1 MI_C51_B1
+#define C5_W2 MI_C51_W2
+#define C5_B2 MI_C51_B2
+#define C5_W3 MI_C51_W3
+#define C5_B3 MI_C51_B3
+#define C5_NP MI_C51_NPARAMS
+#define C5_STRIDE MI_C51_SLAB_STRIDE
+#define C5_W2C 40              // columns of W2 per thread (three threads per row)
+#define C5_STREAM_EXPLORE 3u
+#define C5_STREAM_SAMPLE 4u
+
+// ---- error plumbing of this library ----------------------------------------------------------------
+static thread_local char c5_err[512] = "";
+static void c5_set_error(const char* fmt, ...) {
+    va_list ap;
+    va_start(ap, fmt);
+    vsnprintf(c5_err, sizeof(c5_err), fmt, ap);
+    va_end(ap);
+}
+#define C5_CHECK_ARG(cond, msg)                                       \
+    do {                                                              \
+        if (!(cond)) {                                                \
+            c5_set_error("%s: invalid argument: %s", __func__, msg);  \
+            return MI_C51_EINVAL;                                     \
+        }                                                             \
+    } while (0)
+#define C5_HIP(call)                                                                      \
+    do {                                                                                  \
+        hipError_t e_ = (call);                                                           \
+        if (e_ != hipSuccess) {                                                           \
+            c5_set_error("%s: %s failed: %s", __func__, #call, hipGetErrorString(e_));    \
+            return MI_C51_EHIP;                                                           \
+        }                                                                                 \
+    } while (0)
+
+#ifndef MI_C51_SOURCE_ID
+#define MI_C51_SOURCE_ID "unknown"
+#endif
+extern "C" int mi_c51_version(void) { return MI_C51_VERSION; }
+extern "C" const char* mi_c51_last_error(void) { return c5_err; }
+extern "C" const char* mi_c51_source_id(void) { return MI_C51_SOURCE_ID; }
+static int c5_slabs(int batch) { return batch < MI_C51_MAX_SLABS ? batch : MI_C51_MAX_SLABS; }
+extern "C" size_t mi_c51_workspace_bytes(int batch) {
+    if (batch <= 0) return 0;
+    return (size_t)c5_slabs(batch) * C5_STRIDE * sizeof(float);
+}
+
+// ---- the network as one workgroup holds it ------------------------------------------------------------
+struct c5_weights {
+    float w3[C5_H2]; float b3;          // thread r < 202: row r of W3
+    float w2[C5_W2C]; float b2;         // thread c * 84 + o < 252: W2[o][40 c .. 40 c + 39]; b2 is the chain's start (the bias for c = 0, else 0)
+    float w1[4]; float b1;              // thread u < 120
+};
+struct c5_smem {
+    float h1[C5_H1];
+    float p2[3][C5_H2];                 // layer 2's partial chains; the backward's partial chains of dh2
+    float h2[C5_H2];
+    float logit[2][C5_NA + 3];
+    float q[2];
+    float rowloss;
+    float wl[C5_NA], wu[C5_NA];         // the projection's image (l_j, u_j, wl_j, wu_j)
+    int li[C5_NA], ui[C5_NA];
+    float dl[C5_NA];                    // dlogit of the stored action
+    float dz2[C5_H2];
+    float ph[2][C5_H1];                 // the backward's partial chains of dh1
+};
+
+__device__ __forceinline__ void c5_load_weights(c5_weights& w, const float* __restrict__ P, int t) {
+    {
+        const int r = t < C5_NL ? t : C5_NL - 1;
+        const float4* src = reinterpret_cast<const float4*>(P + C5_W3 + (size_t)r * C5_H2);   // 10,764 and 84 are multiples of 4
+#pragma unroll
+        for (int k = 0; k < C5_H2 / 4; ++k) { const float4 v = src[k]; w.w3[4 * k] = v.x; w.w3[4 * k + 1] = v.y; w.w3[4 * k + 2] = v.z; w.w3[4 * k + 3] = v.w; }
+        w.b3 = P[C5_B3 + r];
+    }
+    {
+        const int tt = t < 3 * C5_H2 ? t : 3 * C5_H2 - 1;
+        const int c = tt / C5_H2, o = tt - c * C5_H2;
+        const float4* src = reinterpret_cast<const float4*>(P + C5_W2 + (size_t)o * C5_H1 + C5_W2C * c);   // 600, 120 and 40 are multiples of 4
+#pragma unroll
+        for (int k = 0; k < C5_W2C / 4; ++k) { const float4 v = src[k]; w.w2[4 * k] = v.x; w.w2[4 * k + 1] = v.y; w.w2[4 * k + 2] = v.z; w.w2[4 * k + 3] = v.w; }
+        w.b2 = c == 0 ? P[C5_B2 + o] : 0.0f;
+    }
+    {
+        const int u = t < C5_H1 ? t : C5_H1 - 1;
+        const float4 v = reinterpret_cast<const float4*>(P + C5_W1)[u];
+        w.w1[0] = v.x; w.w1[1] = v.y; w.w1[2] = v.z; w.w1[3] = v.w;
+        w.b1 = P[C5_B1 + u];
+    }
+}
+
+// the balanced pairwise sum over the 64 lanes in natural order (mi_c51.h: TREE2's second half), result in every lane, VALU only
+__device__ __forceinline__ float c5_wave_sum(float v) {
+    v += dpp_xor1(v);
+    v += dpp_xor2(v);
+    v += dpp_half_mirror(v);
+    v += dpp_mirror(v);
+    return groups_sum(v);
+}
+__device__ __forceinline__ float c5_wave_max(float v) {
+#pragma unroll
+    for (int s = 1; s < 64; s <<= 1) v = fmaxf(v, __shfl_xor(v, s));
+    return v;
+}
+__device__ __forceinline__ float c5_atom(int j) { return MI_C51_V_MIN + 2.0f * (float)j; }
+
+// layers 1 - 3 of one row: sm.h1, sm.h2, sm.logit are valid for every thread when it returns
+__device__ __forceinline__ void c5_forward_row(const c5_weights& w, const float4 x, c5_smem& sm, int t) {
+    if (t < C5_H1) {
+        float z = w.b1;
+        z = __builtin_fmaf(w.w1[0], x.x, z); z = __builtin_fmaf(w.w1[1], x.y, z);
+        z = __builtin_fmaf(w.w1[2], x.z, z); z = __builtin_fmaf(w.w1[3], x.w, z);
+        sm.h1[t] = fmaxf(z, 0.0f);
+    }
+    __syncthreads();
+    if (t < 3 * C5_H2) {
+        const int c = t / C5_H2, o = t - c * C5_H2;
+        float acc = w.b2;
+#pragma unroll
+        for (int k = 0; k < C5_W2C; ++k) acc = __builtin_fmaf(w.w2[k], sm.h1[C5_W2C * c + k], acc);
+        sm.p2[c][o] = acc;
+    }
+    __syncthreads();
+    if (t < C5_H2) sm.h2[t] = fmaxf((sm.p2[0][t] + sm.p2[1][t]) + sm.p2[2][t], 0.0f);
+    __syncthreads();
+    if (t < C5_NL) {
+        float acc = w.b3;
+#pragma unroll
+        for (int k = 0; k < C5_H2; ++k) acc = __builtin_fmaf(w.w3[k], sm.h2[k], acc);
+        const int a = t >= C5_NA ? 1 : 0;
+        sm.logit[a][t - a * C5_NA] = acc;
+    }
+    __syncthreads();
+}
+
+// softmax of action `a`'s logits by ONE wave (all 64 lanes active): lane i gets p_i and p_{i + 64} (0 past atom 100), every lane the action value q.
+__device__ __forceinline__ void c5_softmax_wave(const c5_smem& sm, int a, int lane, float& plo, float& phi, float& q) {
+    const bool hi = lane + 64 < C5_NA;           // the 101-atom axis does not fill two waves: the tail is masked in the max, the sum and every reduction
+    const float llo = sm.logit[a][lane], lhi = hi ? sm.logit[a][lane + 64] : llo;
+    const float m = c5_wave_max(fmaxf(llo, lhi));
+    const float elo = expf(llo - m), ehi = hi ? expf(lhi - m) : 0.0f;
+    const float s = c5_wave_sum(hi ? elo + ehi : elo);
+    plo = elo / s;
+    phi = hi ? ehi / s : 0.0f;
+    q = c5_wave_sum(hi ? __builtin_fmaf(phi, c5_atom(lane + 64), plo * c5_atom(lane)) : plo * c5_atom(lane));
+}
+
+// forward + both softmaxes: waves 0 and 1 return their action's distribution; sm.q valid for every thread on return
+__device__ __forceinline__ void c5_probs_row(const c5_weights& w, const float4 x, c5_smem& sm, int t, float& plo, float& phi) {
+    c5_forward_row(w, x, sm, t);
+    const int wv = t >> 6, lane = t & 63;
+    plo = 0.0f; phi = 0.0f;
+    if (wv < 2) {
+        float q;
+        c5_softmax_wave(sm, wv, lane, plo, phi, q);
+        if (lane == 0) sm.q[wv] = q;
+    }
+    __syncthreads();
+}
+
+// =====================================================================================================
+// forward API
+// =====================================================================================================
+__global__ void __launch_bounds__(256) c51_forward_kernel(const float* __restrict__ params, const float* __restrict__ obs, int n, float* __restrict__ probs,
+                                                          float* __restrict__ q) {
+    __shared__ c5_smem sm;
+    const int t = threadIdx.x, wv = t >> 6, lane = t & 63;
+    c5_weights w;
+    c5_load_weights(w, params, t);
+    for (int row = blockIdx.x; row < n; row += gridDim.x) {
+        const float4 x = reinterpret_cast<const float4*>(obs)[row];
+        float plo, phi;
+        c5_probs_row(w, x, sm, t, plo, phi);
+        if (wv < 2) {
+            if (probs) {
+                float* const dst = probs + ((size_t)row * 2 + wv) * C5_NA;
+                dst[lane] = plo;
+                if (lane + 64 < C5_NA) dst[lane + 64] = phi;
+            }
+            if (q && lane == 0) q[2 * (size_t)row + wv] = sm.q[wv];
+        }
+        __syncthreads();
+    }
+}
+
+// =====================================================================================================
+// acting
+// =====================================================================================================
+struct c5_eps_tab { double v[MI_C51_MAX_STEPS_PER_CALL]; };   // epsilon(global_step + k) in the reference's double arithmetic, passed by value
+
+template <bool FORCED>
+__global__ void __launch_bounds__(256) c51_act_kernel(mi_env e, const float* __restrict__ params, int n_steps, long long global_step, mi_c51_ring_t ring, c5_eps_tab eps,
+                                                      float* __restrict__ obs_cur, const int64_t* __restrict__ forced_actions, const double* __restrict__ forced_resets,
+                                                      mi_episode_t* __restrict__ episodes, int32_t* __restrict__ episode_stats, int max_ep) {
+    __shared__ c5_smem sm;
+    const int t = threadIdx.x;
+    const int N = e.n;
+    const long long slots = ring.slots;
+    c5_weights w;
+    c5_load_weights(w, params, t);
+    int st_cnt = 0, st_len = 0, st_max = 0;
+    for (int n = blockIdx.x; n < N; n += gridDim.x) {
+        // the env's state lives in every thread's registers (uniform across the workgroup); thread 0 does the stores
+        const uint64_t env_id = e.env_id_base + (uint64_t)n;
+        double s0 = e.x[n], s1 = e.x_dot[n], s2 = e.theta[n], s3 = e.theta_dot[n];
+        int elapsed = e.elapsed[n], eplen = e.ep_len[n];
+        float epret = e.ep_ret[n];
+        uint64_t episode = e.episode[n], ctr = e.step_ctr[n];
+        float4 x = reinterpret_cast<const float4*>(obs_cur)[n];
+        // every wave holds env n's state before thread 0 may store the advanced one below: a chunk of exploring or teacher-forced steps has no other barrier, and a
+        // wave that read the advanced step counter would take the greedy branch (and its barriers) apart from the rest of the workgroup
+        __syncthreads();
+        long long slot = global_step % slots;
+        for (int s = 0; s < n_steps; ++s) {
+            int a;
+            if (FORCED && forced_actions) {
+                a = forced_actions[(size_t)s * N + n] != 0 ? 1 : 0;
+            } else {
+                uint32_t r[4];
+                mi_philox(e.seed, env_id, ctr, C5_STREAM_EXPLORE, r);
+                if ((double)mi_u32_to_uniform(r[0]) < eps.v[s]) {
+                    a = (int)(r[1] & 1u);
+                } else {   // uniform branch: the whole workgroup works on this env
+                    float plo, phi;
+                    c5_probs_row(w, x, sm, t, plo, phi);
+                    a = sm.q[1] > sm.q[0] ? 1 : 0;   // torch.argmax: the first index on a tie
+                    __syncthreads();
+                }
+            }
+            int term;
+            mi_cartpole_step(s0, s1, s2, s3, a, term);
+            elapsed += 1; eplen += 1; epret += 1.0f;
+            const bool trunc = !term && elapsed >= CP_MAX_STEPS;
+            const bool done = term || trunc;
+            const int fin_len = eplen; const float fin_ret = epret;
+            if (done) {
+                double rs[4];
+                if (FORCED && forced_resets) {
+#pragma unroll
+                    for (int k = 0; k < 4; ++k) rs[k] = forced_resets[4 * ((size_t)s * N + n) + k];
+                } else {
+                    mi_reset_noise(e.seed, env_id, episode, rs);
+                }
+                episode += 1;
+                s0 = rs[0]; s1 = rs[1]; s2 = rs[2]; s3 = rs[3];
+                elapsed = 0; eplen = 0; epret = 0.0f;
+            }
+            x = make_float4((float)s0, (float)s1, (float)s2, (float)s3);
+            const long long nslot = slot + 1 == slots ? 0 : slot + 1;
+            if (t == 0) {
+                ring.actions[slot * N + n] = a;
+                reinterpret_cast<float4*>(ring.observations)[nslot * N + n] = x;
+                ring.rewards[nslot * N + n] = 1.0f;
+                ring.terminated[nslot * N + n] = (uint8_t)(term ? 1 : 0);
+                if (done) {
+                    st_cnt += 1; st_len += fin_len; st_max = fin_len > st_max ? fin_len : st_max;
+                    if (episode_stats && max_ep > 0) {
+                        const int sl = atomicAdd(episode_stats + 3, 1);
+                        if (sl < max_ep) episodes[sl] = mi_episode_t{n, s, fin_ret, fin_len};
+                    }
+                }
+            }
+            slot = nslot;
+            ctr += 1;
+        }
+        if (t == 0) {
+            e.x[n] = s0; e.x_dot[n] = s1; e.theta[n] = s2; e.theta_dot[n] = s3;
+            e.elapsed[n] = elapsed; e.ep_ret[n] = epret; e.ep_len[n] = eplen; e.episode[n] = episode; e.step_ctr[n] = ctr;
+            reinterpret_cast<float4*>(obs_cur)[n] = x;
+        }
+    }
+    if (t == 0 && episode_stats && st_cnt > 0) { atomicAdd(episode_stats, st_cnt); atomicAdd(episode_stats + 1, st_len); atomicMax(episode_stats + 2, st_max); }
+}
+
+// =====================================================================================================
+// targets, loss, gradient
+// =====================================================================================================
+// next_actions[b] and target_probs[b][:] of ring row `i` (flat index) from the target network held in `w`
+__device__ __forceinline__ void c5_target_row(const c5_weights& w, const mi_c51_ring_t& ring, long long i, float gamma, c5_smem& sm, int t, int32_t* __restrict__ next_action,
+                                              float* __restrict__ m_out) {
+    const long long N = ring.n_envs, total = ring.slots * N;
+    const long long nx = i + N >= total ? i + N - total : i + N;   // ((slot + 1) % slots) * N + env
+    const float4 x = reinterpret_cast<const float4*>(ring.observations)[nx];
+    const float r = ring.rewards[nx];
+    const float live = ring.terminated[nx] ? 0.0f : 1.0f;
+    float plo, phi;
+    c5_probs_row(w, x, sm, t, plo, phi);
+    const int a = sm.q[1] > sm.q[0] ? 1 : 0;
+    const int wv = t >> 6, lane = t & 63;
+    if (wv == a) {
+#pragma unroll
+        for (int h = 0; h < 2; ++h) {
+            const int j = lane + 64 * h;
+            if (j < C5_NA) {
+                const float p = h ? phi : plo;
+                const float tz = fminf(fmaxf(r + (gamma * c5_atom(j)) * live, MI_C51_V_MIN), MI_C51_V_MAX);
+                const float b = (tz + 100.0f) / 2.0f;
+                const float l = floorf(b), u = ceilf(b);
+                sm.li[j] = (int)l; sm.ui[j] = (int)u;
+                sm.wl[j] = ((u + (l == u ? 1.0f : 0.0f)) - b) * p;
+                sm.wu[j] = (b - l) * p;
+            }
+        }
+    }
+    __syncthreads();
+    if (t < C5_NA) {   // per target atom: the lower contributions in ascending j, then the upper ones (index_add_'s order)
+        float m = 0.0f;
+        for (int j = 0; j < C5_NA; ++j) if (sm.li[j] == t) m += sm.wl[j];
+        for (int j = 0; j < C5_NA; ++j) if (sm.ui[j] == t) m += sm.wu[j];
+        m_out[t] = m;
+    }
+    if (t == 0) *next_action = a;
+    __syncthreads();
+}
+
+__global__ void __launch_bounds__(256) c51_target_kernel(const float* __restrict__ target_params, mi_c51_ring_t ring, const int64_t* __restrict__ idx, int batch, float gamma,
+                                                         int32_t* __restrict__ next_actions, float* __restrict__ target_probs) {
+    __shared__ c5_smem sm;
+    const int t = threadIdx.x;
+    const long long total = ring.slots * (long long)ring.n_envs;
+    c5_weights w;
+    c5_load_weights(w, target_params, t);
+    for (int b = blockIdx.x; b < batch; b += gridDim.x) {
+        long long i = idx[b];
+        i = i < 0 ? 0 : (i >= total ? total - 1 : i);   // a bad index reads a valid row, never past the ring
+        c5_target_row(w, ring, i, gamma, sm, t, next_actions + b, target_probs + (size_t)b * C5_NA);
+    }
+}
+
+__global__ void __launch_bounds__(256) c51_grad_kernel(mi_c51_ring_t ring, mi_c51_batch_t bt, float* __restrict__ slabs) {
+    __shared__ c5_smem sm;
+    const int t = threadIdx.x, wv = t >> 6, lane = t & 63;
+    const long long total = ring.slots * (long long)ring.n_envs;
+    c5_weights w;
+    // ---- pass 1, target network: indices, next_actions, target_probs of this workgroup's rows ----
+    c5_load_weights(w, bt.target_params, t);
+    for (int b = blockIdx.x; b < bt.batch; b += gridDim.x) {
+        long long i;
+        if (bt.sample_upper > 0) {
+            uint32_t r[4];
+            mi_philox(bt.sample_seed, bt.sample_update, (uint64_t)b, C5_STREAM_SAMPLE, r);
+            i = (long long)((((uint64_t)r[1] << 32) | r[0]) % (uint64_t)bt.sample_upper);
+            if (t == 0) bt.idx[b] = i;
+        } else {
+            i = bt.idx[b];
+        }
+        i = i < 0 ? 0 : (i >= total ? total - 1 : i);
+        c5_target_row(w, ring, i, bt.gamma, sm, t, bt.next_actions + b, bt.target_probs + (size_t)b * C5_NA);
+    }
+    __threadfence_block();   // pass 2 reads the target_probs this workgroup wrote (c5_target_row ends in a barrier)
+    __syncthreads();
+    // ---- pass 2, online network: forward + backward into register accumulators ----
+    c5_load_weights(w, bt.params, t);
+    float g3[C5_H2], g2[C5_W2C], g1[4] = {0.0f, 0.0f, 0.0f, 0.0f};
+    float gb3 = 0.0f, gb2 = 0.0f, gb1 = 0.0f, loss = 0.0f;
+#pragma unroll
+    for (int k = 0; k < C5_H2; ++k) g3[k] = 0.0f;
+#pragma unroll
+    for (int k = 0; k < C5_W2C; ++k) g2[k] = 0.0f;
+    const float invB = 1.0f / (float)bt.batch;
+    const float* __restrict__ P = bt.params;
+    for (int b = blockIdx.x; b < bt.batch; b += gridDim.x) {
+        long long i;
+        if (bt.sample_upper > 0) {   // recomputed, not re-read
+            uint32_t r[4];
+            mi_philox(bt.sample_seed, bt.sample_update, (uint64_t)b, C5_STREAM_SAMPLE, r);
+            i = (long long)((((uint64_t)r[1] << 32) | r[0]) % (uint64_t)bt.sample_upper);
+        } else {
+            i = bt.idx[b];
+        }
+        i = i < 0 ? 0 : (i >= total ? total - 1 : i);
+        const float4 x = reinterpret_cast<const float4*>(ring.observations)[i];
+        const int a = ring.actions[i] != 0 ? 1 : 0;
+        float plo, phi;
+        c5_probs_row(w, x, sm, t, plo, phi);
+        if (wv == a) {   // one wave, all lanes active
+            const bool hi = lane + 64 < C5_NA;
+            const float* const m = bt.target_probs + (size_t)b * C5_NA;
+            const float mlo = m[lane], mhi = hi ? m[lane + 64] : 0.0f;
+            const float dlo = plo + 1e-8f, dhi = phi + 1e-8f;
+            const float tl = mlo * logf(dlo), th = hi ? mhi * logf(dhi) : 0.0f;
+            const float rowloss = -c5_wave_sum(hi ? tl + th : tl);
+            const float glo = -mlo / dlo, ghi = hi ? -mhi / dhi : 0.0f;
+            const float pl = plo * glo, ph = phi * ghi;
+            const float S = c5_wave_sum(hi ? pl + ph : pl);
+            sm.dl[lane] = (plo * (glo - S)) * invB;
+            if (hi) sm.dl[lane + 64] = (phi * (ghi - S)) * invB;
+            if (lane == 0) sm.rowloss = rowloss;
+            if (bt.probs) {
+                float* const dst = bt.probs + (size_t)b * C5_NA;
+                dst[lane] = plo;
+                if (hi) dst[lane + 64] = phi;
+            }
+        }
+        __syncthreads();
+        if (t == 0) loss += sm.rowloss;
+        // layer 3: thread r owns row r of dW3
+        if (t < C5_NL && (t >= C5_NA ? 1 : 0) == a) {
+            const float d = sm.dl[t - a * C5_NA];
+            gb3 += d;
+#pragma unroll
+            for (int k = 0; k < C5_H2; ++k) g3[k] = __builtin_fmaf(d, sm.h2[k], g3[k]);
+        }
+        // dh2: thread c * 84 + k sums its third of the atoms; W3's column k comes from memory (consecutive threads, consecutive addresses)
+        if (t < 3 * C5_H2) {
+            const int c = t / C5_H2, k = t - c * C5_H2;
+            const int j0 = 34 * c, j1 = j0 + 34 < C5_NA ? j0 + 34 : C5_NA;
+            const float* const col = P + C5_W3 + (size_t)(a * C5_NA) * C5_H2 + k;
+            float acc = 0.0f;
+            for (int j = j0; j < j1; ++j) acc = __builtin_fmaf(sm.dl[j], col[(size_t)j * C5_H2], acc);
+            sm.p2[c][k] = acc;
+        }
+        __syncthreads();
+        if (t < C5_H2) sm.dz2[t] = sm.h2[t] > 0.0f ? (sm.p2[0][t] + sm.p2[1][t]) + sm.p2[2][t] : 0.0f;
+        __syncthreads();
+        if (t < 3 * C5_H2) {
+            const int c = t / C5_H2, o = t - c * C5_H2;
+            const float d = sm.dz2[o];
+            if (c == 0) gb2 += d;
+#pragma unroll
+            for (int k = 0; k < C5_W2C; ++k) g2[k] = __builtin_fmaf(d, sm.h1[C5_W2C * c + k], g2[k]);
+        }
+        if (t < 2 * C5_H1) {
+            const int c = t / C5_H1, k = t - c * C5_H1;
+            const float* const col = P + C5_W2 + k;
+            float acc = 0.0f;
+            for (int o = 42 * c; o < 42 * c + 42; ++o) acc = __builtin_fmaf(sm.dz2[o], col[(size_t)o * C5_H1], acc);
+            sm.ph[c][k] = acc;
+        }
+        __syncthreads();
+        if (t < C5_H1) {
+            const float d = sm.h1[t] > 0.0f ? sm.ph[0][t] + sm.ph[1][t] : 0.0f;
+            gb1 += d;
+            g1[0] = __builtin_fmaf(d, x.x, g1[0]); g1[1] = __builtin_fmaf(d, x.y, g1[1]);
+            g1[2] = __builtin_fmaf(d, x.z, g1[2]); g1[3] = __builtin_fmaf(d, x.w, g1[3]);
+        }
+        __syncthreads();
+    }
+    // ---- the workgroup's slab ----
+    float* const slab = slabs + (size_t)blockIdx.x * C5_STRIDE;
+    if (t < C5_NL) {
+        float4* const dst = reinterpret_cast<float4*>(slab + C5_W3 + (size_t)t * C5_H2);
+#pragma unroll
+        for (int k = 0; k < C5_H2 / 4; ++k) dst[k] = make_float4(g3[4 * k], g3[4 * k + 1], g3[4 * k + 2], g3[4 * k + 3]);
+        slab[C5_B3 + t] = gb3;
+    }
+    if (t < 3 * C5_H2) {
+        const int c = t / C5_H2, o = t - c * C5_H2;
+        float4* const dst = reinterpret_cast<float4*>(slab + C5_W2 + (size_t)o * C5_H1 + C5_W2C * c);
+#pragma unroll
+        for (int k = 0; k < C5_W2C / 4; ++k) dst[k] = make_float4(g2[4 * k], g2[4 * k + 1], g2[4 * k + 2], g2[4 * k + 3]);
+        if (c == 0) slab[C5_B2 + o] = gb2;
+    }
+    if (t < C5_H1) {
+        reinterpret_cast<float4*>(slab + C5_W1)[t] = make_float4(g1[0], g1[1], g1[2], g1[3]);
+        slab[C5_B1 + t] = gb1;
+    }
+    if (t == 0) { slab[C5_NP] = loss; slab[C5_NP + 1] = 0.0f; }
+}
+
+struct c5_adam_consts { float w1, b2, w2, step_size, rbc2, eps; };
+// the host-side coefficients exactly as libmirl's mi_adam forms them
+static c5_adam_consts c5_adam_host(int64_t step, double lr, double beta1, double beta2, double eps) {
+    const double bc1 = 1.0 - pow(beta1, (double)step), bc2 = 1.0 - pow(beta2, (double)step);
+    c5_adam_consts k;
+    k.w1 = (float)(1.0 - beta1); k.b2 = (float)beta2; k.w2 = (float)(1.0 - beta2);
+    k.step_size = (float)(lr / bc1); k.rbc2 = (float)(1.0 / sqrt(bc2)); k.eps = (float)eps;
+    return k;
+}
+
+// 32 elements x 16 slab groups per workgroup: thread (j, k) adds the slabs g = k, k + 16, ... of element j in ascending g on four interleaved accumulators, the 16
+// group sums are then added in ascending k.  Element MI_C51_NPARAMS is the sum of the row losses.
+#define C5_RED_GROUPS 16
+__global__ void __launch_bounds__(32 * C5_RED_GROUPS) c51_reduce_kernel(const float* __restrict__ slabs, int n_slabs, float inv_batch, float* __restrict__ grads,
+                                                                         float* __restrict__ loss, float* __restrict__ p, float* __restrict__ m, float* __restrict__ v,
+                                                                         c5_adam_consts k, int adam) {
+    __shared__ float part[C5_RED_GROUPS][32];
+    const int j = threadIdx.x & 31, grp = threadIdx.x >> 5;
+    const int i = blockIdx.x * 32 + j;
+    float s0 = 0.0f, s1 = 0.0f, s2 = 0.0f, s3 = 0.0f;
+    if (i <= C5_NP) {
+        int g = grp;
+        for (; g + 3 * C5_RED_GROUPS < n_slabs; g += 4 * C5_RED_GROUPS) {
+            s0 += slabs[(size_t)(g + 0 * C5_RED_GROUPS) * C5_STRIDE + i]; s1 += slabs[(size_t)(g + 1 * C5_RED_GROUPS) * C5_STRIDE + i];
+            s2 += slabs[(size_t)(g + 2 * C5_RED_GROUPS) * C5_STRIDE + i]; s3 += slabs[(size_t)(g + 3 * C5_RED_GROUPS) * C5_STRIDE + i];
+        }
+        if (g < n_slabs) s0 += slabs[(size_t)g * C5_STRIDE + i];
+        if (g + C5_RED_GROUPS < n_slabs) s1 += slabs[(size_t)(g + C5_RED_GROUPS) * C5_STRIDE + i];
+        if (g + 2 * C5_RED_GROUPS < n_slabs) s2 += slabs[(size_t)(g + 2 * C5_RED_GROUPS) * C5_STRIDE + i];
+    }
+    part[grp][j] = (s0 + s1) + (s2 + s3);
+    __syncthreads();
+    if (grp != 0 || i > C5_NP) return;
+    float sum = part[0][j];
+#pragma unroll
+    for (int q = 1; q < C5_RED_GROUPS; ++q) sum += part[q][j];
+    if (i == C5_NP) { loss[0] = sum * inv_batch; return; }
+    grads[i] = sum;
+    if (adam) {
+        float mi = m[i], vi = v[i];
+        p[i] = mi_adam_elem(p[i], sum, mi, vi, k.w1, k.b2, k.w2, k.step_size, k.rbc2, k.eps);
+        m[i] = mi; v[i] = vi;
+    }
+}
+
+// ---- C ABI -------------------------------------------------------------------------------------------
+static bool c5_aligned(const void* p) { return ((uintptr_t)p & 15u) == 0; }   // parameters, observations and slabs are read and written as float4
+static int c5_check_ring(const mi_c51_ring_t* r) {
+    C5_CHECK_ARG(r != nullptr, "ring is NULL");
+    C5_CHECK_ARG(r->observations && r->actions && r->rewards && r->terminated, "a ring buffer is NULL");
+    C5_CHECK_ARG(r->slots >= 2 && r->n_envs >= 1, "slots must be >= 2 and n_envs >= 1");
+    C5_CHECK_ARG(c5_aligned(r->observations), "observations must be 16-byte aligned");
+    return MI_C51_OK;
+}
+
+extern "C" int mi_c51_forward(const float* params, const float* obs, int n, float* probs, float* q, void* stream) {
+    C5_CHECK_ARG(params && obs && n > 0 && (probs || q), "bad arguments");
+    C5_CHECK_ARG(c5_aligned(params) && c5_aligned(obs), "params and obs must be 16-byte aligned");
+    c51_forward_kernel<<<n < 1024 ? n : 1024, 256, 0, (hipStream_t)stream>>>(params, obs, n, probs, q);
+    C5_HIP(hipGetLastError());
+    return MI_C51_OK;
+}
+
+extern "C" int mi_c51_act_steps(void* handle, const float* params, int n_steps, int64_t global_step, const mi_c51_ring_t* ring, double start_e, double end_e,
+                                double exploration_fraction, int64_t total_timesteps, float* obs_cur, const int64_t* forced_actions, const double* forced_resets,
+                                mi_episode_t* episodes, int32_t* episode_stats, int max_ep, void* stream) {
+    const mi_env* e = (const mi_env*)handle;
+    C5_CHECK_ARG(e != nullptr && params && obs_cur, "NULL pointer");
+    C5_CHECK_ARG(c5_aligned(params) && c5_aligned(obs_cur), "params and obs_cur must be 16-byte aligned");
+    const int rc = c5_check_ring(ring);
+    if (rc != MI_C51_OK) return rc;
+    C5_CHECK_ARG(e->kind == MI_ENV_CARTPOLE_V1 && e->n > 0, "env is not a CartPole-v1 handle");
+    C5_CHECK_ARG(e->n == ring->n_envs, "the ring's n_envs is not the handle's");
+    C5_CHECK_ARG(n_steps > 0 && n_steps <= MI_C51_MAX_STEPS_PER_CALL, "n_steps must be in [1, 64]");
+    C5_CHECK_ARG(global_step >= 0 && total_timesteps > 0 && exploration_fraction > 0.0, "global_step < 0, total_timesteps <= 0 or exploration_fraction <= 0");
+    C5_CHECK_ARG(max_ep >= 0 && (max_ep == 0 || (episodes && episode_stats)), "episodes / episode_stats buffer missing");
+    hipStream_t s = (hipStream_t)stream;
+    c5_eps_tab tab;
+    const double slope = (end_e - start_e) / (exploration_fraction * (double)total_timesteps);
+    for (int k = 0; k < MI_C51_MAX_STEPS_PER_CALL; ++k) {
+        const double ev = slope * (double)(global_step + k) + start_e;
+        tab.v[k] = ev > end_e ? ev : end_e;
+    }
+    if (episode_stats) C5_HIP(hipMemsetAsync(episode_stats, 0, 4 * sizeof(int32_t), s));
+    const int grid = e->n < 1024 ? e->n : 1024;
+    if (forced_actions || forced_resets)
+        c51_act_kernel<true><<<grid, 256, 0, s>>>(*e, params, n_steps, (long long)global_step, *ring, tab, obs_cur, forced_actions, forced_resets, episodes, episode_stats, max_ep);
+    else
+        c51_act_kernel<false><<<grid, 256, 0, s>>>(*e, params, n_steps, (long long)global_step, *ring, tab, obs_cur, nullptr, nullptr, episodes, episode_stats, max_ep);
+    C5_HIP(hipGetLastError());
+    return MI_C51_OK;
+}
+
+extern "C" int mi_c51_target(const float* target_params, const mi_c51_ring_t* ring, const int64_t* idx, int batch, float gamma, int32_t* next_actions, float* target_probs,
+                             void* stream) {
+    C5_CHECK_ARG(target_params && idx && next_actions && target_probs && batch > 0, "bad arguments");
+    C5_CHECK_ARG(c5_aligned(target_params), "target_params must be 16-byte aligned");
+    const int rc = c5_check_ring(ring);
+    if (rc != MI_C51_OK) return rc;
+    c51_target_kernel<<<batch < 1024 ? batch : 1024, 256, 0, (hipStream_t)stream>>>(target_params, *ring, idx, batch, gamma, next_actions, target_probs);
+    C5_HIP(hipGetLastError());
+    return MI_C51_OK;
+}
+
+static int c5_check_batch(const mi_c51_ring_t* ring, const mi_c51_batch_t* b) {
+    const int rc = c5_check_ring(ring);
+    if (rc != MI_C51_OK) return rc;
+    C5_CHECK_ARG(b != nullptr, "batch is NULL");
+    C5_CHECK_ARG(b->batch > 0, "batch <= 0");
+    C5_CHECK_ARG(b->params && b->target_params && b->idx && b->target_probs && b->next_actions && b->grads && b->loss && b->workspace, "a batch buffer is NULL");
+    C5_CHECK_ARG(c5_aligned(b->params) && c5_aligned(b->target_params) && c5_aligned(b->workspace), "params, target_params and workspace must be 16-byte aligned");
+    C5_CHECK_ARG(b->sample_upper >= 0 && b->sample_upper <= ring->slots * (int64_t)ring->n_envs, "sample_upper outside [0, slots * n_envs]");
+    return MI_C51_OK;
+}
+static int c5_launch_grad(const mi_c51_ring_t* ring, const mi_c51_batch_t* b, float* p, float* m, float* v, const c5_adam_consts& k, int adam, hipStream_t s) {
+    const int slabs = c5_slabs(b->batch);
+    c51_grad_kernel<<<slabs, 256, 0, s>>>(*ring, *b, (float*)b->workspace);
+    C5_HIP(hipGetLastError());
+    if (b->mid_event) C5_HIP(hipEventRecord((hipEvent_t)b->mid_event, s));
+    c51_reduce_kernel<<<(C5_NP + 1 + 31) / 32, 32 * C5_RED_GROUPS, 0, s>>>((const float*)b->workspace, slabs, 1.0f / (float)b->batch, b->grads, b->loss, p, m, v, k, adam);
+    C5_HIP(hipGetLastError());
+    return MI_C51_OK;
+}
+
+extern "C" int mi_c51_grad(const mi_c51_ring_t* ring, const mi_c51_batch_t* b, void* stream) {
+    const int rc = c5_check_batch(ring, b);
+    if (rc != MI_C51_OK) return rc;
+    return c5_launch_grad(ring, b, nullptr, nullptr, nullptr, c5_adam_consts{}, 0, (hipStream_t)stream);
+}
+
+extern "C" int mi_c51_update(const mi_c51_ring_t* ring, const mi_c51_batch_t* b, const mi_c51_adam_t* opt, void* stream) {
+    const int rc = c5_check_batch(ring, b);
+    if (rc != MI_C51_OK) return rc;
+    C5_CHECK_ARG(opt != nullptr, "opt is NULL");
+    C5_CHECK_ARG(opt->exp_avg && opt->exp_avg_sq && opt->step >= 1, "an optimizer buffer is NULL or step < 1");
+    return c5_launch_grad(ring, b, (float*)b->params, opt->exp_avg, opt->exp_avg_sq, c5_adam_host(opt->step, opt->lr, opt->beta1, opt->beta2, opt->eps), 1, (hipStream_t)stream);
+}
