@@ -9,7 +9,7 @@ for gfx950 in ``csrc/`` behind the C ABI of ``include/mi_rl.h``.  There is no CP
 from . import _native  # noqa: F401
 from ._native import set_contraction, get_contraction  # noqa: F401
 from .envs import make, CartPoleVecEnv, PendulumVecEnv  # noqa: F401
-from .agent import ActorCritic, QNetwork, DuelingQNetwork, SoftQNetwork, Actor, DropoutPolicy, C51QNetwork, layer_init, pack  # noqa: F401
+from .agent import ActorCritic, QNetwork, DuelingQNetwork, SoftQNetwork, Actor, DropoutPolicy, C51QNetwork, QRQNetwork, layer_init, pack  # noqa: F401
 from .agent import FeaturesExtractor, CosineEmbeddingNetwork, QuantileNetwork, iqn_forward  # noqa: F401
 from .optim import ClipAdam, Adam  # noqa: F401
 from .engine import PPOEngine  # noqa: F401
@@ -18,6 +18,7 @@ from .sac_engine import SACEngine  # noqa: F401
 from .reinforce_engine import ReinforceEngine  # noqa: F401  (libmirl_pg.so itself loads on first use)
 from .c51_engine import C51Engine  # noqa: F401  (libmirl_c51.so itself loads on first use)
 from .iqn_engine import IQNEngine  # noqa: F401  (libmirl_iqn.so itself loads on first use)
+from .qrdqn_engine import QRDQNEngine  # noqa: F401  (libmirl_qr.so itself loads on first use)
 
 __all__ = ["make", "CartPoleVecEnv", "ActorCritic", "QNetwork", "layer_init", "ClipAdam", "PPOEngine", "DQNEngine",
-           "DuelingQNetwork", "DuelingDQNEngine", "PERDQNEngine", "PendulumVecEnv", "SoftQNetwork", "Actor", "Adam", "SACEngine", "DropoutPolicy", "ReinforceEngine", "C51QNetwork", "C51Engine", "FeaturesExtractor", "CosineEmbeddingNetwork", "QuantileNetwork", "iqn_forward", "IQNEngine", "pack", "set_contraction", "get_contraction"]
+           "DuelingQNetwork", "DuelingDQNEngine", "PERDQNEngine", "PendulumVecEnv", "SoftQNetwork", "Actor", "Adam", "SACEngine", "DropoutPolicy", "ReinforceEngine", "C51QNetwork", "C51Engine", "FeaturesExtractor", "CosineEmbeddingNetwork", "QuantileNetwork", "iqn_forward", "IQNEngine", "QRQNetwork", "QRDQNEngine", "pack", "set_contraction", "get_contraction"]

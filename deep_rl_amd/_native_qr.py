@@ -1,0 +1,88 @@
+"""ctypes binding of libmirl_qr.so — the C ABI declared in include/mi_qr.h (QR-DQN on CartPole-v1).
+
+A fifth library beside libmirl.so, libmirl_pg.so, libmirl_c51.so and libmirl_iqn.so.  It is loaded LAZILY, on the first ``lib()`` call: importing ``deep_rl_amd``
+works with only libmirl.so present, and the first use of the QR-DQN network or engine without a built ``deep_rl_amd/libmirl_qr.so`` raises ``MiError`` — there is
+no fallback.  Build all five with ``make -C deep_rl_amd/csrc``.
+"""
+import ctypes as C
+import os
+
+from ._native import MiError, ptr, stream_ptr  # noqa: F401  (re-exported for the engine)
+
+_HERE = os.path.dirname(os.path.abspath(__file__))
+SO_PATH = os.environ.get("MIRL_QR_SO", os.path.join(_HERE, "libmirl_qr.so"))  # MIRL_QR_SO: A/B and diagnostic builds of the same ABI
+
+ABI_VERSION = 1   # == MI_QR_VERSION of the include/mi_qr.h these signatures and struct layouts were written against
+NPARAMS = 21644
+N_QUANT = 64
+H1, H2 = 120, 84
+OFF_W1, OFF_B1, OFF_W2, OFF_B2, OFF_W3, OFF_B3 = 0, 480, 600, 10680, 10764, 21516
+MAX_SLABS = 128
+SLAB_STRIDE = 21648
+MAX_STEPS_PER_CALL = 64
+MI_QR_OK = 0
+
+
+class QRRing(C.Structure):   # mi_qr_ring_t
+    _fields_ = [("observations", C.c_void_p), ("actions", C.c_void_p), ("rewards", C.c_void_p), ("terminated", C.c_void_p), ("slots", C.c_int64),
+                ("n_envs", C.c_int32), ("reserved", C.c_int32)]
+
+
+class QRAct(C.Structure):   # mi_qr_act_t
+    _fields_ = [(n, C.c_void_p) for n in ("params", "obs_cur", "forced_actions", "forced_resets", "episodes", "episode_stats")] + [
+        ("global_step", C.c_int64), ("total_timesteps", C.c_int64), ("start_e", C.c_double), ("end_e", C.c_double), ("exploration_fraction", C.c_double),
+        ("n_steps", C.c_int32), ("max_ep", C.c_int32)]
+
+
+class QRBatch(C.Structure):   # mi_qr_batch_t
+    _fields_ = [(n, C.c_void_p) for n in ("params", "target_params", "idx", "current", "target", "next_actions", "grads", "loss", "workspace")] + [
+        ("sample_seed", C.c_uint64), ("sample_update", C.c_uint64), ("sample_upper", C.c_int64), ("batch", C.c_int32), ("gamma", C.c_float), ("mid_event", C.c_void_p)]
+
+
+class QRAdam(C.Structure):   # mi_qr_adam_t
+    _fields_ = [("exp_avg", C.c_void_p), ("exp_avg_sq", C.c_void_p), ("step", C.c_int64), ("lr", C.c_double), ("beta1", C.c_double), ("beta2", C.c_double),
+                ("eps", C.c_double)]
+
+
+_VP, _I, _SZ = C.c_void_p, C.c_int, C.c_size_t
+SIGNATURES = {
+    "mi_qr_version": (_I, []),
+    "mi_qr_last_error": (C.c_char_p, []),
+    "mi_qr_source_id": (C.c_char_p, []),
+    "mi_qr_workspace_bytes": (_SZ, [_I]),
+    "mi_qr_forward": (_I, [_VP, _VP, _I, _VP, _VP, _VP]),
+    "mi_qr_act_steps": (_I, [_VP, C.POINTER(QRRing), C.POINTER(QRAct), _VP]),
+    "mi_qr_target": (_I, [C.POINTER(QRRing), C.POINTER(QRBatch), _VP]),
+    "mi_qr_quantile_huber": (_I, [_VP, _VP, _I, _VP, _VP, _VP]),
+    "mi_qr_grad": (_I, [C.POINTER(QRRing), C.POINTER(QRBatch), _VP]),
+    "mi_qr_update": (_I, [C.POINTER(QRRing), C.POINTER(QRBatch), C.POINTER(QRAdam), _VP]),
+}
+
+_lib = None
+
+
+def lib():
+    """Load libmirl_qr.so (once, on first use).  Fails loudly: the HIP library is not optional for the QR-DQN path."""
+    global _lib
+    if _lib is None:
+        if not os.path.exists(SO_PATH):
+            raise MiError("deep_rl_amd: %s is missing — build it with `make -C deep_rl_amd/csrc` (hipcc --offload-arch=gfx950); there is no CPU fallback" % SO_PATH)
+        L = C.CDLL(SO_PATH)
+        for name, (res, args) in SIGNATURES.items():
+            fn = getattr(L, name)
+            fn.restype, fn.argtypes = res, args
+        got = L.mi_qr_version()
+        if got != ABI_VERSION:
+            raise MiError("deep_rl_amd: %s reports ABI version %d, this binding is written against %d — rebuild it (make -C deep_rl_amd/csrc)" % (SO_PATH, got, ABI_VERSION))
+        _lib = L
+    return _lib
+
+
+def check(rc, what=""):
+    if rc != MI_QR_OK:
+        msg = lib().mi_qr_last_error()
+        raise MiError("%s failed (rc=%d): %s" % (what or "libmirl_qr call", rc, msg.decode() if msg else "?"))
+
+
+def source_id():
+    return lib().mi_qr_source_id().decode()

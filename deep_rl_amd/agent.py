@@ -325,6 +325,44 @@ class C51QNetwork(_FlatModule):
         return self._run(observation, False, True)[1]
 
 
+class QRQNetwork(_FlatModule):
+    """The QR-DQN network (4 -> 120 -> 84 -> n_actions * n_quantiles, ReLU, Unflatten, torch default init) over one flat fp32 device buffer of 21,644 floats
+    (include/mi_qr.h).  The layer list is the plain ``nn.Sequential``'s, so ``torch.manual_seed(s)`` before construction gives its initial weights bit for bit.
+    The kernels are specialised for CartPole and 64 quantiles."""
+
+    def __init__(self, env, n_quantiles=64, device=None):
+        super().__init__()
+        from . import _native_qr as K
+        obs_dim = int(np.prod(env.observation_space.shape))
+        if obs_dim != 4 or getattr(env.action_space, "n", None) != 2:
+            raise N.MiError("the HIP kernels are specialised for CartPole (obs 4, actions 2)")
+        if int(n_quantiles) != K.N_QUANT:
+            raise N.MiError("the QR-DQN kernels are specialised for n_quantiles = %d; got %r" % (K.N_QUANT, n_quantiles))
+        self.network = nn.Sequential(nn.Linear(obs_dim, 120), nn.ReLU(), nn.Linear(120, 84), nn.ReLU(), nn.Linear(84, env.action_space.n * n_quantiles),
+                                     nn.Unflatten(-1, (env.action_space.n, n_quantiles)))
+        self.n_quantiles = int(n_quantiles)
+        self._finish(env, device, K.NPARAMS)
+
+    def _run(self, observation, want_quantiles, want_q):
+        from . import _native_qr as K
+        obs = observation.to(self.device, torch.float32)
+        lead = obs.shape[:-1]
+        obs = obs.reshape(-1, 4).contiguous()
+        n = obs.shape[0]
+        quant = torch.empty((n, 2, K.N_QUANT), dtype=torch.float32, device=self.device) if want_quantiles else None
+        q = torch.empty((n, 2), dtype=torch.float32, device=self.device) if want_q else None
+        K.check(K.lib().mi_qr_forward(N.ptr(self.flat), N.ptr(obs), n, N.ptr(quant), N.ptr(q), N.stream_ptr(self.device)), "mi_qr_forward")
+        return (quant.reshape(*lead, 2, K.N_QUANT) if want_quantiles else None), (q.reshape(*lead, 2) if want_q else None)
+
+    def get_quantiles(self, observation):
+        """The 64 quantiles of both actions: [..., 2, 64]."""
+        return self._run(observation, True, False)[0]
+
+    def get_q_values(self, observation):
+        """The mean of the quantiles, through the collapsed head (include/mi_qr.h): [..., 2]."""
+        return self._run(observation, False, True)[1]
+
+
 def _cpu_only(module):
     """The single IQN modules have no kernel of their own: the library evaluates the three together (``iqn_forward``, IQNEngine).  Their ``forward`` is for
     inspecting a network on the CPU; on a device it is an error, never a quiet torch evaluation."""
