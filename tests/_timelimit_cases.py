@@ -21,6 +21,12 @@ that step (`_find_subseed`).  With 1,100 steps, starts 51 and 99 give everything
 7-call); 99 -> steps 598 (last of a 49+50s call, middle of a 50-call) and 1098 (last of a 7-call).
 The 520-step case (1,030 envs) cannot hold an env that is truncated twice, nor a truncation on the first step of a 50-call (step 500: an episode of one step);
 tests/test_timelimit_cases_cpu.py asserts every other condition for it.
+
+PPO (tests/test_gpu_timelimit_ppo.py).  rollout_q4_kernel keeps `elapsed` in a register for a launch of T steps and carries it from launch to launch through the env
+handle.  `Case.ppo_storage` is what the (T + 1, N) storage must hold after the launch that runs steps g0 ... g0 + T - 1; `ppo_launches` the launch lengths of a case
+at a given T; `PPO_WRONG_RULES` the ways that copy of the rule can be wrong (restate: `carry_every`, `truncate`); `controller_ppo` an ActorCritic vector whose
+stochastic policy balances the pole; `ppo64` the float64 forward; `MEASURED_PPO_*` the oracle's own f32 distance from it, from which the device bounds follow.
+The case "ppo64" (64 envs) is PPO's grid of 16 four-env workgroups, a multiple of 8, on which the XCD-aware env-group map permutes.
 """
 import functools
 
@@ -131,6 +137,20 @@ class Case:
         act[ga % slots] = self.actions[ga]
         return dict(observations=obs, actions=act, rewards=rew, terminated=term)
 
+    def ppo_storage(self, g0, T):
+        """what PPO's (T + 1, N) storage must hold after the rollout that runs steps g0 ... g0 + T - 1 (ppo.py:113-141): observations[r] = obs[g0 + r] (the row behind a
+        done step holds the RESET observation), actions[r] = the action of step g0 + r, rewards[r] = 1 and dones[r] = done[g0 + r - 1] for r >= 1 — PPO stores `done`,
+        truncations included, not `terminated`.  `unwritten`: per tensor the (T + 1,) mask of the rows a launch never writes (rewards[0], dones[0], actions[T],
+        log_probs[T], as tests/test_gpu_poison.py has it); the values given here for those rows mean nothing"""
+        n = self.n
+        act = np.zeros((T + 1, n), np.int64); rew = np.zeros((T + 1, n), np.float32); dn = np.zeros((T + 1, n), np.float32)
+        act[:T] = self.actions[g0:g0 + T]
+        rew[1:] = 1.0
+        dn[1:] = self.done[g0:g0 + T]
+        first = np.arange(T + 1) == 0; last = np.arange(T + 1) == T; none = np.zeros(T + 1, bool)
+        return dict(observations=self.obs[g0:g0 + T + 1].copy(), actions=act, rewards=rew, dones=dn,
+                    unwritten=dict(observations=none, values=none, actions=last, log_probs=last, rewards=first, dones=first))
+
     def episodes(self, g0, k):
         """the episode log of the call that runs steps g0 ... g0 + k - 1: [(env, step in call, return, length)] in (step, env) order"""
         out = []
@@ -230,6 +250,8 @@ _FIVE = (K0, K1A, K1B, K2, K3)
 def _spec(name):
     if name == "dqn37":     # 16-env workgroups with a ragged tail; positions 0, 15, 16 and 36 are long-episode envs (kinds 0, 0, 1a, 1a)
         return dict(n=37, steps=1100, kinds=[_FIVE[i % 5] for i in range(37)], starts={3: 51, 8: 99})
+    if name == "ppo64":     # PPO's rollout launch: 16 workgroups of 4 envs — a multiple of 8, so the XCD-aware env-group map permutes — below MI_STATS_PART_MIN (32)
+        return dict(n=64, steps=1100, kinds=[_FIVE[i % 5] for i in range(64)], starts={3: 51, 8: 99})
     if name == "n5":        # one env per workgroup: one of each long kind, the two kind-2 envs give the phases (their random stretch supplies the short episodes)
         return dict(n=5, steps=1100, kinds=[K0, K1A, K1B, K2, K2], starts={3: 51, 4: 99})
     if name == "n1030":     # the grid is capped at 1,024 workgroups: workgroups 0 - 5 walk envs (w, 1024 + w); those twelve are long-episode envs with different outcomes
@@ -242,7 +264,7 @@ def _spec(name):
 
 
 SHARED_1030 = tuple(range(6)) + tuple(range(1024, 1030))
-NAMES = ("dqn37", "n5", "n1030")
+NAMES = ("dqn37", "n5", "n1030", "ppo64")
 
 
 @functools.lru_cache(maxsize=None)
@@ -268,10 +290,13 @@ def replay(R, n, seed, base, actions, resets_at=()):
 
 
 # ---- the limit rule restated, with the ways it can be wrong ---------------------------------------------------
-def restate(R, case, envs, limit=LIMIT, terminated_is_done=False, zero_on_termination=True):
+def restate(R, case, envs, limit=LIMIT, terminated_is_done=False, zero_on_termination=True, carry_every=None, truncate=True):
     """TimeLimit + auto-reset around R.cartpole_step for the envs `envs` of `case` under its action table and its resets:
-    -> (terminated u8 [steps][len(envs)], observations f32 [steps + 1][len(envs)][4]).  The defaults are the true rule."""
+    -> (terminated u8 [steps][len(envs)], observations f32 [steps + 1][len(envs)][4], done bool [steps][len(envs)]).  The defaults are the true rule.
+    carry_every = T: `elapsed` is zeroed in front of every T-th step (a rollout launch of T steps that does not carry it over from the launch before);
+    truncate = False: `done := terminated`, a truncation neither flagged nor reset."""
     term_out = np.zeros((case.steps, len(envs)), np.uint8); obs_out = np.zeros((case.steps + 1, len(envs), 4), np.float32)
+    done_out = np.zeros((case.steps, len(envs)), bool)
     table = case.forced_table
     with _Mode(R):
         for c, i in enumerate(envs):
@@ -279,18 +304,21 @@ def restate(R, case, envs, limit=LIMIT, terminated_is_done=False, zero_on_termin
             obs_out[0, c] = s
             elapsed, k = 0, 0
             for g in range(case.steps):
+                if carry_every and g % carry_every == 0:
+                    elapsed = 0
                 s, term = R.cartpole_step(s, int(case.actions[g, i]))
                 elapsed += 1
-                trunc = (not term) and elapsed >= limit
+                trunc = truncate and (not term) and elapsed >= limit
                 done = term or trunc
                 term_out[g, c] = done if terminated_is_done else term
+                done_out[g, c] = done
                 if done:
                     s = table[i, k] if table is not None else R.reset_noise(case.seed, case.base + i, k + 1)
                     k += 1
                     if trunc or zero_on_termination:
                         elapsed = 0
                 obs_out[g + 1, c] = s
-    return term_out, obs_out
+    return term_out, obs_out, done_out
 
 
 WRONG_RULES = {
@@ -299,6 +327,31 @@ WRONG_RULES = {
     "limit 501": dict(limit=LIMIT + 1),
     "elapsed not zeroed after a termination": dict(zero_on_termination=False),
 }
+
+
+# PPO's rollout launch (rollout_q4_kernel).  `terminated := done` is no wrong rule for it: PPO stores `done` (ppo.py:141).  `elapsed` lives in a register for a whole
+# launch and crosses launches through the env handle: "T" stands for the launch length (ppo_wrong_rules)
+PPO_WRONG_RULES = {
+    "limit 499": dict(limit=LIMIT - 1),
+    "limit 501": dict(limit=LIMIT + 1),
+    "elapsed not zeroed after a termination": dict(zero_on_termination=False),
+    "elapsed not carried across launches": dict(carry_every="T"),
+    "done := terminated": dict(truncate=False),
+}
+
+
+def ppo_wrong_rules(T):
+    """PPO_WRONG_RULES as restate() keywords for launches of T steps"""
+    return {label: {k: (T if v == "T" else v) for k, v in kw.items()} for label, kw in PPO_WRONG_RULES.items()}
+
+
+def ppo_launches(steps, T):
+    """the launch lengths of PPO's view of a case: the floor(steps / T) whole rollouts; where those end in front of step 499, so that nothing can be truncated in them
+    (1,030 envs x 520 steps at T = 300: ONE launch), one more launch takes the steps that are left"""
+    out = [T] * (steps // T)
+    if sum(out) < LIMIT and steps % T:
+        out.append(steps % T)
+    return out
 
 
 # ---- controller networks: q_1 - q_0 = K (w . obs) ---------------------------------------------------------------
@@ -385,3 +438,75 @@ def close_q(algo):
 
 CONTROLLERS = {"dqn": controller_dqn, "dueling": controller_dueling, "c51": controller_c51, "iqn": controller_iqn}
 CONTROLLER_K = 16.0   # |q_1 - q_0| = K |w . obs|: tests/test_timelimit_cases_cpu.py shows that under the rule fewer than 1 % of the decisions lie inside close_q
+
+
+# ---- PPO: an ActorCritic (4 -> 64 -> 64 -> 2 | 4 -> 64 -> 64 -> 1, tanh) that follows the rule with a margin ---------------------------------------------------
+PPO_NPARAMS, PPO_CRITIC = 9155, 4610      # include/mi_rl.h "Parameter layout": per net W1[unit][obs], b1, W2, b2, W3[out][unit], b3; the critic behind the actor
+PPO_C, PPO_K = 50.0, 6.0
+
+
+def _orthogonal(rng, rows, cols, gain):
+    """torch.nn.init.orthogonal_'s construction (QR of a normal draw, signs of R's diagonal) from a numpy generator"""
+    a = rng.normal(size=(max(rows, cols), min(rows, cols)))
+    q, r = np.linalg.qr(a)
+    q = q * np.sign(np.diag(r))
+    return (gain * (q if rows >= cols else q.T)).astype(np.float32)
+
+
+def controller_ppo(c=PPO_C, K=PPO_K, critic_seed=17):
+    """actor: unit 0 of layer 1 is tanh(c w . obs), carried through unit 0 of layer 2 (W2[0][0] = 1) to the logits -+K/2: l_1 - l_0 = K tanh(tanh(c w . obs)), every
+    other actor weight zero.  It is a stochastic policy that takes the rule's action with probability >= 1 / (1 + exp(-K tanh(tanh(c |w . obs|)))) — about 10 % of
+    the actions go against the rule without dropping the pole — and |log_prob| <= log(1 + exp(K tanh(tanh(inf)))) = 4.58.  The critic is a default-init draw
+    (orthogonal, gains sqrt 2, sqrt 2, 1; zero biases: ppo.py:25-47) from a fixed seed, so that the values are no constants."""
+    p = np.zeros(PPO_NPARAMS, np.float32)
+    W1 = p[0:256].reshape(64, 4); W2 = p[320:4416].reshape(64, 64); W3 = p[4480:4608].reshape(2, 64)
+    W1[0] = c * RULE_W
+    W2[0, 0] = 1
+    W3[1, 0] = K / 2; W3[0, 0] = -K / 2
+    rng = np.random.default_rng(critic_seed)
+    cr = p[PPO_CRITIC:]
+    cr[0:256] = _orthogonal(rng, 64, 4, np.sqrt(2)).reshape(-1)
+    cr[320:4416] = _orthogonal(rng, 64, 64, np.sqrt(2)).reshape(-1)
+    cr[4480:4544] = _orthogonal(rng, 1, 64, 1.0).reshape(-1)
+    return p
+
+
+def ppo64(p, obs):
+    """float64 forward of a flat ActorCritic vector on f32 observations -> (logits [rows][2], log-softmax [rows][2], values [rows])"""
+    p = np.asarray(p, np.float32).astype(np.float64); X = np.asarray(obs, np.float32).astype(np.float64).reshape(-1, 4)
+
+    def net(q, nout):
+        h1 = np.tanh(X @ q[0:256].reshape(64, 4).T + q[256:320])
+        h2 = np.tanh(h1 @ q[320:4416].reshape(64, 64).T + q[4416:4480])
+        return h2 @ q[4480:4480 + 64 * nout].reshape(nout, 64).T + q[4480 + 64 * nout:4480 + 65 * nout]
+
+    logits = net(p[:PPO_CRITIC], 2)
+    m = logits.max(axis=1, keepdims=True)
+    logp = logits - (m + np.log(np.exp(logits - m).sum(axis=1, keepdims=True)))
+    return logits, logp, net(p[PPO_CRITIC:], 1)[:, 0]
+
+
+def ppo_noisy_params(seed=5):
+    """default init plus noise, as tests/test_gpu_parity.py's test_rollout_production_rng_vs_oracle has it (a larger actor head: the log-probs are no constants);
+    drawn with numpy, so that the CPU measurement and the GPU tests hold the same vector"""
+    rng = np.random.default_rng([seed, 9155])
+    p = np.zeros(PPO_NPARAMS, np.float32)
+    for base, nout, gain in ((0, 2, 0.01), (PPO_CRITIC, 1, 1.0)):
+        q = p[base:]
+        q[0:256] = _orthogonal(rng, 64, 4, np.sqrt(2)).reshape(-1)
+        q[320:4416] = _orthogonal(rng, 64, 64, np.sqrt(2)).reshape(-1)
+        q[4480:4480 + 64 * nout] = _orthogonal(rng, nout, 64, gain).reshape(-1)
+    idx = np.arange(PPO_NPARAMS)
+    return (p + rng.normal(0, 0.3, PPO_NPARAMS) * (idx >= 4480) * (idx < PPO_CRITIC)).astype(np.float32)
+
+
+# The oracle's f32 log-probs (R.actor -> R.categorical) and values (R.critic) against ppo64 on the observations each vector meets in the GPU tests (tests/test_timelimit_cases_cpu.py
+# test_ppo_logprob_and_value_bounds_rest_on_the_oracle measures them again and holds them against these figures): the largest absolute distance over both parameter
+# vectors.  The device bounds are max(3e-6, 8 x measured): 3e-6 is tests/test_gpu_parity.py's bound for values and log-probs at default-init scale, 8 the project's
+# factor over a measured restatement distance.
+MEASURED_PPO_LOGP = 1.2e-6     # measured 1.188e-06 (default init plus noise; the controller on its own run: 1.083e-06) -> device bound 9.6e-6
+MEASURED_PPO_VALUE = 4.0e-7    # measured 3.906e-07 (default init plus noise; the controller's critic: 1.129e-07) -> device bound 3.2e-6
+
+
+def ppo_bounds():
+    return max(3e-6, 8 * MEASURED_PPO_LOGP), max(3e-6, 8 * MEASURED_PPO_VALUE)

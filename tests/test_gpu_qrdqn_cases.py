@@ -14,7 +14,7 @@ import _qrdqn_cases as K
 import _qrdqn_ref as X
 import _timelimit_cases as T
 from test_gpu_qrdqn import _make, _np, _record
-from test_gpu_timelimit import _check_call, _check_ring, _run_forced, _snapshot, _start
+from test_gpu_timelimit import _check_call, _check_ring, _checkpoint_inside_a_long_episode, _reset_case, _reset_inside_an_episode, _run_forced, _snapshot, _start
 
 pytestmark = pytest.mark.gpu
 f32 = np.float32
@@ -196,3 +196,15 @@ def test_greedy_controller_runs_into_the_limit(dev):
     far = np.abs(q[:, 1] - q[:, 0]) >= X.CLOSE_Q
     assert (~far).mean() <= 0.01, int((~far).sum())
     assert np.array_equal(actions.reshape(-1)[far], (q[:, 1] > q[:, 0]).astype(np.int64)[far])
+
+
+def test_checkpoint_inside_a_long_episode(dev, tmp_path):
+    """saved at global step 300 of the 5-env case, loaded into a fresh engine whose env was driven somewhere else, continued to step 620: ring, `elapsed`, log and
+    statistics equal the uninterrupted run bit for bit, and the truncation comes at step 500 (the body of tests/test_gpu_timelimit.py's test)"""
+    _checkpoint_inside_a_long_episode(lambda n, slots, params=None: _tl_make(dev, n, slots, params=params), T.get("n5", False), X.NPARAMS, str(tmp_path / "qrdqn"), "qrdqn")
+
+
+def test_reset_inside_an_episode_restarts_the_limit(dev):
+    """300 balanced steps, reset(), 520 more: no truncation at step 500, every env truncated 500 steps after the reset"""
+    from oracle import cpu_ref as R
+    _reset_inside_an_episode(lambda n, slots: _tl_make(dev, n, slots), _reset_case(R, 5), "qrdqn")

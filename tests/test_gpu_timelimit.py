@@ -206,34 +206,40 @@ def test_greedy_controller_runs_into_the_limit(dev, R, kind):
 
 
 # ---- d. checkpoint inside a long episode --------------------------------------------------------------------------
-@pytest.mark.parametrize("kind", ["dqn_log", "c51", "iqn"])
-def test_checkpoint_inside_a_long_episode(dev, kind, tmp_path):
-    """saved at global step 300, loaded into a fresh engine (zeroed parameters; its env first driven somewhere else: other state, `elapsed`, episode and step
-    counters) and continued to step 620: ring, `elapsed`, log and statistics equal the uninterrupted run bit for bit, and the truncation comes at step 500.
-    (checkpoint.load refuses an env of another seed by design — the keys of every later reset belong to the seed — so the fresh engine's env has the same seed.)"""
+def _checkpoint_inside_a_long_episode(make, case, nparams, path, label):
+    """the body of the test below for any ring engine; make(n, slots, params=None) builds one (tests/test_gpu_qrdqn_cases.py runs it on QRDQNEngine)"""
     import torch
 
     from deep_rl_amd import checkpoint
-    case = T.get("dqn37" if kind in DQN_FAMILY else "n5", False)
     assert {T.K0, T.K1A, T.K1B} <= set(case.kinds.tolist()) and case.trunc[499].any() and not case.trunc[300:499].any()
     slots = 64
     rng = np.random.default_rng(3)
-    a = _make(dev, kind, case.n, slots, params=rng.normal(0, 0.05, {"dqn": 10934, "c51": 27934, "iqn": 44898}[ALGO[kind]]).astype(np.float32))
+    a = make(case.n, slots, params=rng.normal(0, 0.05, nparams).astype(np.float32))
     _start(a, case)
-    _run_forced(a, case, T.calls("50", 300), slots, False, (kind, "before"))
-    path = checkpoint.save(str(tmp_path / kind), a)
-    b = _make(dev, kind, case.n, slots)
+    _run_forced(a, case, T.calls("50", 300), slots, False, (label, "before"))
+    path = checkpoint.save(path, a)
+    b = make(case.n, slots)
     b.reset()
     b.act(13, forced_actions=torch.zeros((13, case.n), dtype=torch.int64))
     assert not np.array_equal(_np(b.env.get_state()[1]), case.elapsed[300])
     checkpoint.load(path, b)
     assert b.global_step == 300 and np.array_equal(_np(b.q.flat), _np(a.q.flat)) and np.array_equal(_np(b.env.get_state()[1]), case.elapsed[300])
     for eng, tag in ((a, "uninterrupted"), (b, "resumed")):
-        assert _run_forced(eng, case, T.calls("50", 320), slots, True, (kind, tag), g0=300) == 620
+        assert _run_forced(eng, case, T.calls("50", 320), slots, True, (label, tag), g0=300) == 620
     for f in FIELDS + ("observation",):
         assert np.array_equal(_np(getattr(a, f)), _np(getattr(b, f))), f
     for x, y in zip(a.env.get_state(), b.env.get_state()):
         assert np.array_equal(_np(x), _np(y))
+
+
+@pytest.mark.parametrize("kind", ["dqn_log", "c51", "iqn"])
+def test_checkpoint_inside_a_long_episode(dev, kind, tmp_path):
+    """saved at global step 300, loaded into a fresh engine (zeroed parameters; its env first driven somewhere else: other state, `elapsed`, episode and step
+    counters) and continued to step 620: ring, `elapsed`, log and statistics equal the uninterrupted run bit for bit, and the truncation comes at step 500.
+    (checkpoint.load refuses an env of another seed by design — the keys of every later reset belong to the seed — so the fresh engine's env has the same seed.)"""
+    case = T.get("dqn37" if kind in DQN_FAMILY else "n5", False)
+    _checkpoint_inside_a_long_episode(lambda n, slots, params=None: _make(dev, kind, n, slots, params=params), case,
+                                      {"dqn": 10934, "c51": 27934, "iqn": 44898}[ALGO[kind]], str(tmp_path / kind), kind)
 
 
 # ---- e. reset() inside an episode ---------------------------------------------------------------------------------
@@ -252,13 +258,11 @@ def _reset_case(R, n):
     return _RESET_CASES[n]
 
 
-@pytest.mark.parametrize("kind", ["dqn_lazy", "dqn_log", "c51", "iqn"])
-def test_reset_inside_an_episode_restarts_the_limit(dev, R, kind):
-    """300 balanced steps, reset(), 520 more: no truncation at step 500, every env truncated 500 steps after the reset, as the oracle's reset() has it"""
-    case = _reset_case(R, 37 if kind in DQN_FAMILY else 5)
+def _reset_inside_an_episode(make, case, label):
+    """the body of the test below for any ring engine; make(n, slots) builds one"""
     assert case.truncation_steps() == [(799, e) for e in range(case.n)] and (case.fin_len[799] == 500).all() and (case.elapsed[500] == 200).all()
     slots = 64
-    eng = _make(dev, kind, case.n, slots)
+    eng = make(case.n, slots)
     _start(eng, case)
     # the record holds the observation reset() left in front of step 300; the one the 300th step produced is checked here
     import torch
@@ -268,5 +272,12 @@ def test_reset_inside_an_episode_restarts_the_limit(dev, R, kind):
         g += k
     assert (_np(eng.env.get_state()[1]) == 300).all()
     assert np.array_equal(_np(eng.reset()), case.obs[300]) and (_np(eng.env.get_state()[1]) == 0).all()
-    _run_forced(eng, case, T.calls("50", 520), slots, True, (kind, "after reset"), g0=300)
+    _run_forced(eng, case, T.calls("50", 520), slots, True, (label, "after reset"), g0=300)
+
+
+@pytest.mark.parametrize("kind", ["dqn_lazy", "dqn_log", "c51", "iqn"])
+def test_reset_inside_an_episode_restarts_the_limit(dev, R, kind):
+    """300 balanced steps, reset(), 520 more: no truncation at step 500, every env truncated 500 steps after the reset, as the oracle's reset() has it"""
+    case = _reset_case(R, 37 if kind in DQN_FAMILY else 5)
+    _reset_inside_an_episode(lambda n, slots: _make(dev, kind, n, slots), case, kind)
     _record("e_reset", kind, case)
