@@ -195,6 +195,37 @@ def lib():
     return _lib
 
 
+def lazy_binding(so_path, signatures, abi_version, prefix, what):
+    """-> (lib, check, source_id) of one of the libraries beside libmirl.so (`prefix` "mi_c51": libmirl_c51.so, whose symbols are mi_c51_*).  `lib` loads it once, on
+    first use, so importing the package needs only libmirl.so; a missing file, a missing symbol and another ABI version are loud errors, never a fallback."""
+    name, loaded = "libmirl" + prefix[2:], []
+
+    def lib():
+        if not loaded:
+            if not os.path.exists(so_path):
+                raise MiError("deep_rl_amd: %s is missing — build it with `make -C deep_rl_amd/csrc` (hipcc --offload-arch=gfx950); there is no CPU fallback" % so_path)
+            L = C.CDLL(so_path)
+            for sym, (res, args) in signatures.items():
+                fn = getattr(L, sym)
+                fn.restype, fn.argtypes = res, args
+            got = getattr(L, prefix + "_version")()
+            if got != abi_version:
+                raise MiError("deep_rl_amd: %s reports ABI version %d, this binding is written against %d — rebuild it (make -C deep_rl_amd/csrc)" % (so_path, got, abi_version))
+            loaded.append(L)
+        return loaded[0]
+
+    def check(rc, what=""):
+        if rc != MI_OK:
+            msg = getattr(lib(), prefix + "_last_error")()
+            raise MiError("%s failed (rc=%d): %s" % (what or name + " call", rc, msg.decode() if msg else "?"))
+
+    def source_id():
+        return getattr(lib(), prefix + "_source_id")().decode()
+
+    lib.__doc__ = "Load %s.so (once, on first use).  Fails loudly: the HIP library is not optional for the %s path." % (name, what)
+    return lib, check, source_id
+
+
 CONTRACTIONS = ("f32", "bf16x3")   # == enum MI_CONTRACTION_* of include/mi_rl.h
 
 

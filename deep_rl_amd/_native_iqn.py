@@ -7,7 +7,7 @@ Build all four with ``make -C deep_rl_amd/csrc``.
 import ctypes as C
 import os
 
-from ._native import MiError, ptr, stream_ptr  # noqa: F401  (re-exported for the engine)
+from ._native import MiError, lazy_binding, ptr, stream_ptr  # noqa: F401  (MiError, ptr, stream_ptr: re-exported for the engine)
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 SO_PATH = os.environ.get("MIRL_IQN_SO", os.path.join(_HERE, "libmirl_iqn.so"))  # MIRL_IQN_SO: A/B and diagnostic builds of the same ABI
@@ -61,31 +61,19 @@ SIGNATURES = {
     "mi_iqn_update": (_I, [C.POINTER(IQNRing), C.POINTER(IQNBatch), C.POINTER(IQNAdam), _VP]),
 }
 
-_lib = None
+lib, check, source_id = lazy_binding(SO_PATH, SIGNATURES, ABI_VERSION, "mi_iqn", "IQN")
+
+# what RingEngine (_ring_engine.py) drives, under the same names in every ring-replay binding
+Ring, Batch, AdamArgs = IQNRing, IQNBatch, IQNAdam
 
 
-def lib():
-    """Load libmirl_iqn.so (once, on first use).  Fails loudly: the HIP library is not optional for the IQN path."""
-    global _lib
-    if _lib is None:
-        if not os.path.exists(SO_PATH):
-            raise MiError("deep_rl_amd: %s is missing — build it with `make -C deep_rl_amd/csrc` (hipcc --offload-arch=gfx950); there is no CPU fallback" % SO_PATH)
-        L = C.CDLL(SO_PATH)
-        for name, (res, args) in SIGNATURES.items():
-            fn = getattr(L, name)
-            fn.restype, fn.argtypes = res, args
-        got = L.mi_iqn_version()
-        if got != ABI_VERSION:
-            raise MiError("deep_rl_amd: %s reports ABI version %d, this binding is written against %d — rebuild it (make -C deep_rl_amd/csrc)" % (SO_PATH, got, ABI_VERSION))
-        _lib = L
-    return _lib
+def workspace_bytes(batch):
+    return lib().mi_iqn_workspace_bytes(batch)
 
 
-def check(rc, what=""):
-    if rc != MI_IQN_OK:
-        msg = lib().mi_iqn_last_error()
-        raise MiError("%s failed (rc=%d): %s" % (what or "libmirl_iqn call", rc, msg.decode() if msg else "?"))
+def grad(ring, batch, stream):
+    check(lib().mi_iqn_grad(C.byref(ring), C.byref(batch), stream), "mi_iqn_grad")
 
 
-def source_id():
-    return lib().mi_iqn_source_id().decode()
+def update(ring, batch, adam, stream):
+    check(lib().mi_iqn_update(C.byref(ring), C.byref(batch), C.byref(adam), stream), "mi_iqn_update")

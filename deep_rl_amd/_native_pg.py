@@ -6,7 +6,7 @@ use of the REINFORCE engine without a built ``deep_rl_amd/libmirl_pg.so`` raises
 import ctypes as C
 import os
 
-from ._native import MiError, ptr, stream_ptr  # noqa: F401  (re-exported for the engine)
+from ._native import MiError, lazy_binding, ptr, stream_ptr  # noqa: F401  (MiError, ptr, stream_ptr: re-exported for the engine)
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 SO_PATH = os.environ.get("MIRL_PG_SO", os.path.join(_HERE, "libmirl_pg.so"))  # MIRL_PG_SO: A/B and diagnostic builds of the same ABI
@@ -46,31 +46,4 @@ SIGNATURES = {
     "mi_pg_update": (_I, [_VP, C.POINTER(PGBuffers), C.POINTER(PGHparams), _VP]),
 }
 
-_lib = None
-
-
-def lib():
-    """Load libmirl_pg.so (once, on first use).  Fails loudly: the HIP library is not optional for the REINFORCE path."""
-    global _lib
-    if _lib is None:
-        if not os.path.exists(SO_PATH):
-            raise MiError("deep_rl_amd: %s is missing — build it with `make -C deep_rl_amd/csrc` (hipcc --offload-arch=gfx950); there is no CPU fallback" % SO_PATH)
-        L = C.CDLL(SO_PATH)
-        for name, (res, args) in SIGNATURES.items():
-            fn = getattr(L, name)
-            fn.restype, fn.argtypes = res, args
-        got = L.mi_pg_version()
-        if got != ABI_VERSION:
-            raise MiError("deep_rl_amd: %s reports ABI version %d, this binding is written against %d — rebuild it (make -C deep_rl_amd/csrc)" % (SO_PATH, got, ABI_VERSION))
-        _lib = L
-    return _lib
-
-
-def check(rc, what=""):
-    if rc != MI_PG_OK:
-        msg = lib().mi_pg_last_error()
-        raise MiError("%s failed (rc=%d): %s" % (what or "libmirl_pg call", rc, msg.decode() if msg else "?"))
-
-
-def source_id():
-    return lib().mi_pg_source_id().decode()
+lib, check, source_id = lazy_binding(SO_PATH, SIGNATURES, ABI_VERSION, "mi_pg", "REINFORCE")

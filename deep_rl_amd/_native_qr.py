@@ -7,7 +7,7 @@ no fallback.  Build all five with ``make -C deep_rl_amd/csrc``.
 import ctypes as C
 import os
 
-from ._native import MiError, ptr, stream_ptr  # noqa: F401  (re-exported for the engine)
+from ._native import MiError, lazy_binding, ptr, stream_ptr  # noqa: F401  (MiError, ptr, stream_ptr: re-exported for the engine)
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 SO_PATH = os.environ.get("MIRL_QR_SO", os.path.join(_HERE, "libmirl_qr.so"))  # MIRL_QR_SO: A/B and diagnostic builds of the same ABI
@@ -58,31 +58,19 @@ SIGNATURES = {
     "mi_qr_update": (_I, [C.POINTER(QRRing), C.POINTER(QRBatch), C.POINTER(QRAdam), _VP]),
 }
 
-_lib = None
+lib, check, source_id = lazy_binding(SO_PATH, SIGNATURES, ABI_VERSION, "mi_qr", "QR-DQN")
+
+# what RingEngine (_ring_engine.py) drives, under the same names in every ring-replay binding
+Ring, Batch, AdamArgs = QRRing, QRBatch, QRAdam
 
 
-def lib():
-    """Load libmirl_qr.so (once, on first use).  Fails loudly: the HIP library is not optional for the QR-DQN path."""
-    global _lib
-    if _lib is None:
-        if not os.path.exists(SO_PATH):
-            raise MiError("deep_rl_amd: %s is missing — build it with `make -C deep_rl_amd/csrc` (hipcc --offload-arch=gfx950); there is no CPU fallback" % SO_PATH)
-        L = C.CDLL(SO_PATH)
-        for name, (res, args) in SIGNATURES.items():
-            fn = getattr(L, name)
-            fn.restype, fn.argtypes = res, args
-        got = L.mi_qr_version()
-        if got != ABI_VERSION:
-            raise MiError("deep_rl_amd: %s reports ABI version %d, this binding is written against %d — rebuild it (make -C deep_rl_amd/csrc)" % (SO_PATH, got, ABI_VERSION))
-        _lib = L
-    return _lib
+def workspace_bytes(batch):
+    return lib().mi_qr_workspace_bytes(batch)
 
 
-def check(rc, what=""):
-    if rc != MI_QR_OK:
-        msg = lib().mi_qr_last_error()
-        raise MiError("%s failed (rc=%d): %s" % (what or "libmirl_qr call", rc, msg.decode() if msg else "?"))
+def grad(ring, batch, stream):
+    check(lib().mi_qr_grad(C.byref(ring), C.byref(batch), stream), "mi_qr_grad")
 
 
-def source_id():
-    return lib().mi_qr_source_id().decode()
+def update(ring, batch, adam, stream):
+    check(lib().mi_qr_update(C.byref(ring), C.byref(batch), C.byref(adam), stream), "mi_qr_update")

@@ -10,10 +10,9 @@
 // All arithmetic on the VALU in fp32 with the summation orders of the header; no floating-point atomics.
 // Uses mi_common.h read-only for the device helpers; none of its host-side macros (they call into libmirl.so).
 #include "mi_common.h"
+#include "mi_ring.h"
 
 #include "../../include/mi_c51.h"
-
-#include <stdarg.h>
 
 #define C5_H1 MI_C51_H1
 #define C5_H2 MI_C51_H2
@@ -28,40 +27,15 @@
 #define C5_NP MI_C51_NPARAMS
 #define C5_STRIDE MI_C51_SLAB_STRIDE
 #define C5_W2C 40              // columns of W2 per thread (three threads per row)
-#define C5_STREAM_EXPLORE 3u
-#define C5_STREAM_SAMPLE 4u
-
-// ---- error plumbing of this library ----------------------------------------------------------------
-static thread_local char c5_err[512] = "";
-static void c5_set_error(const char* fmt, ...) {
-    va_list ap;
-    va_start(ap, fmt);
-    vsnprintf(c5_err, sizeof(c5_err), fmt, ap);
-    va_end(ap);
-}
-#define C5_CHECK_ARG(cond, msg)                                       \
-    do {                                                              \
-        if (!(cond)) {                                                \
-            c5_set_error("%s: invalid argument: %s", __func__, msg);  \
-            return MI_C51_EINVAL;                                     \
-        }                                                             \
-    } while (0)
-#define C5_HIP(call)                                                                      \
-    do {                                                                                  \
-        hipError_t e_ = (call);                                                           \
-        if (e_ != hipSuccess) {                                                           \
-            c5_set_error("%s: %s failed: %s", __func__, #call, hipGetErrorString(e_));    \
-            return MI_C51_EHIP;                                                           \
-        }                                                                                 \
-    } while (0)
+static_assert(MI_C51_OK == RG_OK && MI_C51_EINVAL == RG_EINVAL && MI_C51_EHIP == RG_EHIP && MI_C51_MAX_STEPS_PER_CALL == RG_MAX_STEPS, "mi_ring.h returns these");
 
 #ifndef MI_C51_SOURCE_ID
 #define MI_C51_SOURCE_ID "unknown"
 #endif
 extern "C" int mi_c51_version(void) { return MI_C51_VERSION; }
-extern "C" const char* mi_c51_last_error(void) { return c5_err; }
+extern "C" const char* mi_c51_last_error(void) { return rg_err; }
 extern "C" const char* mi_c51_source_id(void) { return MI_C51_SOURCE_ID; }
-static int c5_slabs(int batch) { return batch < MI_C51_MAX_SLABS ? batch : MI_C51_MAX_SLABS; }
+static int c5_slabs(int batch) { return rg_slabs(batch, MI_C51_MAX_SLABS); }
 extern "C" size_t mi_c51_workspace_bytes(int batch) {
     if (batch <= 0) return 0;
     return (size_t)c5_slabs(batch) * C5_STRIDE * sizeof(float);
@@ -208,90 +182,31 @@ __global__ void __launch_bounds__(256) c51_forward_kernel(const float* __restric
 // =====================================================================================================
 // acting
 // =====================================================================================================
-struct c5_eps_tab { double v[MI_C51_MAX_STEPS_PER_CALL]; };   // epsilon(global_step + k) in the reference's double arithmetic, passed by value
+// the greedy action of rg_act_loop: the whole network is resident in `w`
+struct c5_policy {
+    const c5_weights& w;
+    c5_smem& sm;
+    int t;
+    __device__ __forceinline__ int greedy(const float4& x, int, int, uint64_t, uint64_t) {
+        float plo, phi;
+        c5_probs_row(w, x, sm, t, plo, phi);
+        const int a = sm.q[1] > sm.q[0] ? 1 : 0;   // torch.argmax: the first index on a tie
+        __syncthreads();
+        return a;
+    }
+};
 
 template <bool FORCED>
-__global__ void __launch_bounds__(256) c51_act_kernel(mi_env e, const float* __restrict__ params, int n_steps, long long global_step, mi_c51_ring_t ring, c5_eps_tab eps,
+__global__ void __launch_bounds__(256) c51_act_kernel(mi_env e, const float* __restrict__ params, int n_steps, long long global_step, mi_c51_ring_t ring, rg_eps_tab eps,
                                                       float* __restrict__ obs_cur, const int64_t* __restrict__ forced_actions, const double* __restrict__ forced_resets,
                                                       mi_episode_t* __restrict__ episodes, int32_t* __restrict__ episode_stats, int max_ep) {
     __shared__ c5_smem sm;
     const int t = threadIdx.x;
-    const int N = e.n;
-    const long long slots = ring.slots;
     c5_weights w;
     c5_load_weights(w, params, t);
-    int st_cnt = 0, st_len = 0, st_max = 0;
-    for (int n = blockIdx.x; n < N; n += gridDim.x) {
-        // the env's state lives in every thread's registers (uniform across the workgroup); thread 0 does the stores
-        const uint64_t env_id = e.env_id_base + (uint64_t)n;
-        double s0 = e.x[n], s1 = e.x_dot[n], s2 = e.theta[n], s3 = e.theta_dot[n];
-        int elapsed = e.elapsed[n], eplen = e.ep_len[n];
-        float epret = e.ep_ret[n];
-        uint64_t episode = e.episode[n], ctr = e.step_ctr[n];
-        float4 x = reinterpret_cast<const float4*>(obs_cur)[n];
-        // every wave holds env n's state before thread 0 may store the advanced one below: a chunk of exploring or teacher-forced steps has no other barrier, and a
-        // wave that read the advanced step counter would take the greedy branch (and its barriers) apart from the rest of the workgroup
-        __syncthreads();
-        long long slot = global_step % slots;
-        for (int s = 0; s < n_steps; ++s) {
-            int a;
-            if (FORCED && forced_actions) {
-                a = forced_actions[(size_t)s * N + n] != 0 ? 1 : 0;
-            } else {
-                uint32_t r[4];
-                mi_philox(e.seed, env_id, ctr, C5_STREAM_EXPLORE, r);
-                if ((double)mi_u32_to_uniform(r[0]) < eps.v[s]) {
-                    a = (int)(r[1] & 1u);
-                } else {   // uniform branch: the whole workgroup works on this env
-                    float plo, phi;
-                    c5_probs_row(w, x, sm, t, plo, phi);
-                    a = sm.q[1] > sm.q[0] ? 1 : 0;   // torch.argmax: the first index on a tie
-                    __syncthreads();
-                }
-            }
-            int term;
-            mi_cartpole_step(s0, s1, s2, s3, a, term);
-            elapsed += 1; eplen += 1; epret += 1.0f;
-            const bool trunc = !term && elapsed >= CP_MAX_STEPS;
-            const bool done = term || trunc;
-            const int fin_len = eplen; const float fin_ret = epret;
-            if (done) {
-                double rs[4];
-                if (FORCED && forced_resets) {
-#pragma unroll
-                    for (int k = 0; k < 4; ++k) rs[k] = forced_resets[4 * ((size_t)s * N + n) + k];
-                } else {
-                    mi_reset_noise(e.seed, env_id, episode, rs);
-                }
-                episode += 1;
-                s0 = rs[0]; s1 = rs[1]; s2 = rs[2]; s3 = rs[3];
-                elapsed = 0; eplen = 0; epret = 0.0f;
-            }
-            x = make_float4((float)s0, (float)s1, (float)s2, (float)s3);
-            const long long nslot = slot + 1 == slots ? 0 : slot + 1;
-            if (t == 0) {
-                ring.actions[slot * N + n] = a;
-                reinterpret_cast<float4*>(ring.observations)[nslot * N + n] = x;
-                ring.rewards[nslot * N + n] = 1.0f;
-                ring.terminated[nslot * N + n] = (uint8_t)(term ? 1 : 0);
-                if (done) {
-                    st_cnt += 1; st_len += fin_len; st_max = fin_len > st_max ? fin_len : st_max;
-                    if (episode_stats && max_ep > 0) {
-                        const int sl = atomicAdd(episode_stats + 3, 1);
-                        if (sl < max_ep) episodes[sl] = mi_episode_t{n, s, fin_ret, fin_len};
-                    }
-                }
-            }
-            slot = nslot;
-            ctr += 1;
-        }
-        if (t == 0) {
-            e.x[n] = s0; e.x_dot[n] = s1; e.theta[n] = s2; e.theta_dot[n] = s3;
-            e.elapsed[n] = elapsed; e.ep_ret[n] = epret; e.ep_len[n] = eplen; e.episode[n] = episode; e.step_ctr[n] = ctr;
-            reinterpret_cast<float4*>(obs_cur)[n] = x;
-        }
-    }
-    if (t == 0 && episode_stats && st_cnt > 0) { atomicAdd(episode_stats, st_cnt); atomicAdd(episode_stats + 1, st_len); atomicMax(episode_stats + 2, st_max); }
+    c5_policy policy{w, sm, t};
+    const rg_act_args a{obs_cur, forced_actions, forced_resets, episodes, episode_stats, global_step, 0, n_steps, max_ep};
+    rg_act_loop<FORCED>(e, ring, a, eps, policy);
 }
 
 // =====================================================================================================
@@ -357,16 +272,7 @@ __global__ void __launch_bounds__(256) c51_grad_kernel(mi_c51_ring_t ring, mi_c5
     // ---- pass 1, target network: indices, next_actions, target_probs of this workgroup's rows ----
     c5_load_weights(w, bt.target_params, t);
     for (int b = blockIdx.x; b < bt.batch; b += gridDim.x) {
-        long long i;
-        if (bt.sample_upper > 0) {
-            uint32_t r[4];
-            mi_philox(bt.sample_seed, bt.sample_update, (uint64_t)b, C5_STREAM_SAMPLE, r);
-            i = (long long)((((uint64_t)r[1] << 32) | r[0]) % (uint64_t)bt.sample_upper);
-            if (t == 0) bt.idx[b] = i;
-        } else {
-            i = bt.idx[b];
-        }
-        i = i < 0 ? 0 : (i >= total ? total - 1 : i);
+        const long long i = rg_row_index(bt.sample_seed, bt.sample_update, bt.sample_upper, bt.idx, b, total, t == 0);
         c5_target_row(w, ring, i, bt.gamma, sm, t, bt.next_actions + b, bt.target_probs + (size_t)b * C5_NA);
     }
     __threadfence_block();   // pass 2 reads the target_probs this workgroup wrote (c5_target_row ends in a barrier)
@@ -382,15 +288,7 @@ __global__ void __launch_bounds__(256) c51_grad_kernel(mi_c51_ring_t ring, mi_c5
     const float invB = 1.0f / (float)bt.batch;
     const float* __restrict__ P = bt.params;
     for (int b = blockIdx.x; b < bt.batch; b += gridDim.x) {
-        long long i;
-        if (bt.sample_upper > 0) {   // recomputed, not re-read
-            uint32_t r[4];
-            mi_philox(bt.sample_seed, bt.sample_update, (uint64_t)b, C5_STREAM_SAMPLE, r);
-            i = (long long)((((uint64_t)r[1] << 32) | r[0]) % (uint64_t)bt.sample_upper);
-        } else {
-            i = bt.idx[b];
-        }
-        i = i < 0 ? 0 : (i >= total ? total - 1 : i);
+        const long long i = rg_row_index(bt.sample_seed, bt.sample_update, bt.sample_upper, bt.idx, b, total, false);   // recomputed, not re-read
         const float4 x = reinterpret_cast<const float4*>(ring.observations)[i];
         const int a = ring.actions[i] != 0 ? 1 : 0;
         float plo, phi;
@@ -480,66 +378,18 @@ __global__ void __launch_bounds__(256) c51_grad_kernel(mi_c51_ring_t ring, mi_c5
     if (t == 0) { slab[C5_NP] = loss; slab[C5_NP + 1] = 0.0f; }
 }
 
-struct c5_adam_consts { float w1, b2, w2, step_size, rbc2, eps; };
-// the host-side coefficients exactly as libmirl's mi_adam forms them
-static c5_adam_consts c5_adam_host(int64_t step, double lr, double beta1, double beta2, double eps) {
-    const double bc1 = 1.0 - pow(beta1, (double)step), bc2 = 1.0 - pow(beta2, (double)step);
-    c5_adam_consts k;
-    k.w1 = (float)(1.0 - beta1); k.b2 = (float)beta2; k.w2 = (float)(1.0 - beta2);
-    k.step_size = (float)(lr / bc1); k.rbc2 = (float)(1.0 / sqrt(bc2)); k.eps = (float)eps;
-    return k;
-}
-
-// 32 elements x 16 slab groups per workgroup: thread (j, k) adds the slabs g = k, k + 16, ... of element j in ascending g on four interleaved accumulators, the 16
-// group sums are then added in ascending k.  Element MI_C51_NPARAMS is the sum of the row losses.
-#define C5_RED_GROUPS 16
-__global__ void __launch_bounds__(32 * C5_RED_GROUPS) c51_reduce_kernel(const float* __restrict__ slabs, int n_slabs, float inv_batch, float* __restrict__ grads,
+__global__ void __launch_bounds__(32 * RG_RED_GROUPS) c51_reduce_kernel(const float* __restrict__ slabs, int n_slabs, float inv_batch, float* __restrict__ grads,
                                                                          float* __restrict__ loss, float* __restrict__ p, float* __restrict__ m, float* __restrict__ v,
-                                                                         c5_adam_consts k, int adam) {
-    __shared__ float part[C5_RED_GROUPS][32];
-    const int j = threadIdx.x & 31, grp = threadIdx.x >> 5;
-    const int i = blockIdx.x * 32 + j;
-    float s0 = 0.0f, s1 = 0.0f, s2 = 0.0f, s3 = 0.0f;
-    if (i <= C5_NP) {
-        int g = grp;
-        for (; g + 3 * C5_RED_GROUPS < n_slabs; g += 4 * C5_RED_GROUPS) {
-            s0 += slabs[(size_t)(g + 0 * C5_RED_GROUPS) * C5_STRIDE + i]; s1 += slabs[(size_t)(g + 1 * C5_RED_GROUPS) * C5_STRIDE + i];
-            s2 += slabs[(size_t)(g + 2 * C5_RED_GROUPS) * C5_STRIDE + i]; s3 += slabs[(size_t)(g + 3 * C5_RED_GROUPS) * C5_STRIDE + i];
-        }
-        if (g < n_slabs) s0 += slabs[(size_t)g * C5_STRIDE + i];
-        if (g + C5_RED_GROUPS < n_slabs) s1 += slabs[(size_t)(g + C5_RED_GROUPS) * C5_STRIDE + i];
-        if (g + 2 * C5_RED_GROUPS < n_slabs) s2 += slabs[(size_t)(g + 2 * C5_RED_GROUPS) * C5_STRIDE + i];
-    }
-    part[grp][j] = (s0 + s1) + (s2 + s3);
-    __syncthreads();
-    if (grp != 0 || i > C5_NP) return;
-    float sum = part[0][j];
-#pragma unroll
-    for (int q = 1; q < C5_RED_GROUPS; ++q) sum += part[q][j];
-    if (i == C5_NP) { loss[0] = sum * inv_batch; return; }
-    grads[i] = sum;
-    if (adam) {
-        float mi = m[i], vi = v[i];
-        p[i] = mi_adam_elem(p[i], sum, mi, vi, k.w1, k.b2, k.w2, k.step_size, k.rbc2, k.eps);
-        m[i] = mi; v[i] = vi;
-    }
+                                                                         rg_adam_consts k, int adam) {
+    rg_reduce<C5_NP, C5_STRIDE>(slabs, n_slabs, inv_batch, grads, loss, p, m, v, k, adam);
 }
 
 // ---- C ABI -------------------------------------------------------------------------------------------
-static bool c5_aligned(const void* p) { return ((uintptr_t)p & 15u) == 0; }   // parameters, observations and slabs are read and written as float4
-static int c5_check_ring(const mi_c51_ring_t* r) {
-    C5_CHECK_ARG(r != nullptr, "ring is NULL");
-    C5_CHECK_ARG(r->observations && r->actions && r->rewards && r->terminated, "a ring buffer is NULL");
-    C5_CHECK_ARG(r->slots >= 2 && r->n_envs >= 1, "slots must be >= 2 and n_envs >= 1");
-    C5_CHECK_ARG(c5_aligned(r->observations), "observations must be 16-byte aligned");
-    return MI_C51_OK;
-}
-
 extern "C" int mi_c51_forward(const float* params, const float* obs, int n, float* probs, float* q, void* stream) {
-    C5_CHECK_ARG(params && obs && n > 0 && (probs || q), "bad arguments");
-    C5_CHECK_ARG(c5_aligned(params) && c5_aligned(obs), "params and obs must be 16-byte aligned");
+    RG_CHECK_ARG(params && obs && n > 0 && (probs || q), "bad arguments");
+    RG_CHECK_ARG(rg_aligned(params) && rg_aligned(obs), "params and obs must be 16-byte aligned");
     c51_forward_kernel<<<n < 1024 ? n : 1024, 256, 0, (hipStream_t)stream>>>(params, obs, n, probs, q);
-    C5_HIP(hipGetLastError());
+    RG_HIP(hipGetLastError());
     return MI_C51_OK;
 }
 
@@ -547,73 +397,69 @@ extern "C" int mi_c51_act_steps(void* handle, const float* params, int n_steps, 
                                 double exploration_fraction, int64_t total_timesteps, float* obs_cur, const int64_t* forced_actions, const double* forced_resets,
                                 mi_episode_t* episodes, int32_t* episode_stats, int max_ep, void* stream) {
     const mi_env* e = (const mi_env*)handle;
-    C5_CHECK_ARG(e != nullptr && params && obs_cur, "NULL pointer");
-    C5_CHECK_ARG(c5_aligned(params) && c5_aligned(obs_cur), "params and obs_cur must be 16-byte aligned");
-    const int rc = c5_check_ring(ring);
+    RG_CHECK_ARG(e != nullptr && params && obs_cur, "NULL pointer");
+    RG_CHECK_ARG(rg_aligned(params) && rg_aligned(obs_cur), "params and obs_cur must be 16-byte aligned");
+    const int rc = rg_check_ring(ring);
     if (rc != MI_C51_OK) return rc;
-    C5_CHECK_ARG(e->kind == MI_ENV_CARTPOLE_V1 && e->n > 0, "env is not a CartPole-v1 handle");
-    C5_CHECK_ARG(e->n == ring->n_envs, "the ring's n_envs is not the handle's");
-    C5_CHECK_ARG(n_steps > 0 && n_steps <= MI_C51_MAX_STEPS_PER_CALL, "n_steps must be in [1, 64]");
-    C5_CHECK_ARG(global_step >= 0 && total_timesteps > 0 && exploration_fraction > 0.0, "global_step < 0, total_timesteps <= 0 or exploration_fraction <= 0");
-    C5_CHECK_ARG(max_ep >= 0 && (max_ep == 0 || (episodes && episode_stats)), "episodes / episode_stats buffer missing");
+    RG_CHECK_ARG(e->kind == MI_ENV_CARTPOLE_V1 && e->n > 0, "env is not a CartPole-v1 handle");
+    RG_CHECK_ARG(e->n == ring->n_envs, "the ring's n_envs is not the handle's");
+    RG_CHECK_ARG(n_steps > 0 && n_steps <= MI_C51_MAX_STEPS_PER_CALL, "n_steps must be in [1, 64]");
+    RG_CHECK_ARG(global_step >= 0 && total_timesteps > 0 && exploration_fraction > 0.0, "global_step < 0, total_timesteps <= 0 or exploration_fraction <= 0");
+    RG_CHECK_ARG(max_ep >= 0 && (max_ep == 0 || (episodes && episode_stats)), "episodes / episode_stats buffer missing");
     hipStream_t s = (hipStream_t)stream;
-    c5_eps_tab tab;
-    const double slope = (end_e - start_e) / (exploration_fraction * (double)total_timesteps);
-    for (int k = 0; k < MI_C51_MAX_STEPS_PER_CALL; ++k) {
-        const double ev = slope * (double)(global_step + k) + start_e;
-        tab.v[k] = ev > end_e ? ev : end_e;
-    }
-    if (episode_stats) C5_HIP(hipMemsetAsync(episode_stats, 0, 4 * sizeof(int32_t), s));
+    rg_eps_tab tab;
+    rg_eps_fill(tab, global_step, (end_e - start_e) / (exploration_fraction * (double)total_timesteps), start_e, end_e);
+    if (episode_stats) RG_HIP(hipMemsetAsync(episode_stats, 0, 4 * sizeof(int32_t), s));
     const int grid = e->n < 1024 ? e->n : 1024;
     if (forced_actions || forced_resets)
         c51_act_kernel<true><<<grid, 256, 0, s>>>(*e, params, n_steps, (long long)global_step, *ring, tab, obs_cur, forced_actions, forced_resets, episodes, episode_stats, max_ep);
     else
         c51_act_kernel<false><<<grid, 256, 0, s>>>(*e, params, n_steps, (long long)global_step, *ring, tab, obs_cur, nullptr, nullptr, episodes, episode_stats, max_ep);
-    C5_HIP(hipGetLastError());
+    RG_HIP(hipGetLastError());
     return MI_C51_OK;
 }
 
 extern "C" int mi_c51_target(const float* target_params, const mi_c51_ring_t* ring, const int64_t* idx, int batch, float gamma, int32_t* next_actions, float* target_probs,
                              void* stream) {
-    C5_CHECK_ARG(target_params && idx && next_actions && target_probs && batch > 0, "bad arguments");
-    C5_CHECK_ARG(c5_aligned(target_params), "target_params must be 16-byte aligned");
-    const int rc = c5_check_ring(ring);
+    RG_CHECK_ARG(target_params && idx && next_actions && target_probs && batch > 0, "bad arguments");
+    RG_CHECK_ARG(rg_aligned(target_params), "target_params must be 16-byte aligned");
+    const int rc = rg_check_ring(ring);
     if (rc != MI_C51_OK) return rc;
     c51_target_kernel<<<batch < 1024 ? batch : 1024, 256, 0, (hipStream_t)stream>>>(target_params, *ring, idx, batch, gamma, next_actions, target_probs);
-    C5_HIP(hipGetLastError());
+    RG_HIP(hipGetLastError());
     return MI_C51_OK;
 }
 
 static int c5_check_batch(const mi_c51_ring_t* ring, const mi_c51_batch_t* b) {
-    const int rc = c5_check_ring(ring);
+    const int rc = rg_check_ring(ring);
     if (rc != MI_C51_OK) return rc;
-    C5_CHECK_ARG(b != nullptr, "batch is NULL");
-    C5_CHECK_ARG(b->batch > 0, "batch <= 0");
-    C5_CHECK_ARG(b->params && b->target_params && b->idx && b->target_probs && b->next_actions && b->grads && b->loss && b->workspace, "a batch buffer is NULL");
-    C5_CHECK_ARG(c5_aligned(b->params) && c5_aligned(b->target_params) && c5_aligned(b->workspace), "params, target_params and workspace must be 16-byte aligned");
-    C5_CHECK_ARG(b->sample_upper >= 0 && b->sample_upper <= ring->slots * (int64_t)ring->n_envs, "sample_upper outside [0, slots * n_envs]");
+    RG_CHECK_ARG(b != nullptr, "batch is NULL");
+    RG_CHECK_ARG(b->batch > 0, "batch <= 0");
+    RG_CHECK_ARG(b->params && b->target_params && b->idx && b->target_probs && b->next_actions && b->grads && b->loss && b->workspace, "a batch buffer is NULL");
+    RG_CHECK_ARG(rg_aligned(b->params) && rg_aligned(b->target_params) && rg_aligned(b->workspace), "params, target_params and workspace must be 16-byte aligned");
+    RG_CHECK_ARG(b->sample_upper >= 0 && b->sample_upper <= ring->slots * (int64_t)ring->n_envs, "sample_upper outside [0, slots * n_envs]");
     return MI_C51_OK;
 }
-static int c5_launch_grad(const mi_c51_ring_t* ring, const mi_c51_batch_t* b, float* p, float* m, float* v, const c5_adam_consts& k, int adam, hipStream_t s) {
+static int c5_launch_grad(const mi_c51_ring_t* ring, const mi_c51_batch_t* b, float* p, float* m, float* v, const rg_adam_consts& k, int adam, hipStream_t s) {
     const int slabs = c5_slabs(b->batch);
     c51_grad_kernel<<<slabs, 256, 0, s>>>(*ring, *b, (float*)b->workspace);
-    C5_HIP(hipGetLastError());
-    if (b->mid_event) C5_HIP(hipEventRecord((hipEvent_t)b->mid_event, s));
-    c51_reduce_kernel<<<(C5_NP + 1 + 31) / 32, 32 * C5_RED_GROUPS, 0, s>>>((const float*)b->workspace, slabs, 1.0f / (float)b->batch, b->grads, b->loss, p, m, v, k, adam);
-    C5_HIP(hipGetLastError());
+    RG_HIP(hipGetLastError());
+    if (b->mid_event) RG_HIP(hipEventRecord((hipEvent_t)b->mid_event, s));
+    c51_reduce_kernel<<<(C5_NP + 1 + 31) / 32, 32 * RG_RED_GROUPS, 0, s>>>((const float*)b->workspace, slabs, 1.0f / (float)b->batch, b->grads, b->loss, p, m, v, k, adam);
+    RG_HIP(hipGetLastError());
     return MI_C51_OK;
 }
 
 extern "C" int mi_c51_grad(const mi_c51_ring_t* ring, const mi_c51_batch_t* b, void* stream) {
     const int rc = c5_check_batch(ring, b);
     if (rc != MI_C51_OK) return rc;
-    return c5_launch_grad(ring, b, nullptr, nullptr, nullptr, c5_adam_consts{}, 0, (hipStream_t)stream);
+    return c5_launch_grad(ring, b, nullptr, nullptr, nullptr, rg_adam_consts{}, 0, (hipStream_t)stream);
 }
 
 extern "C" int mi_c51_update(const mi_c51_ring_t* ring, const mi_c51_batch_t* b, const mi_c51_adam_t* opt, void* stream) {
     const int rc = c5_check_batch(ring, b);
     if (rc != MI_C51_OK) return rc;
-    C5_CHECK_ARG(opt != nullptr, "opt is NULL");
-    C5_CHECK_ARG(opt->exp_avg && opt->exp_avg_sq && opt->step >= 1, "an optimizer buffer is NULL or step < 1");
-    return c5_launch_grad(ring, b, (float*)b->params, opt->exp_avg, opt->exp_avg_sq, c5_adam_host(opt->step, opt->lr, opt->beta1, opt->beta2, opt->eps), 1, (hipStream_t)stream);
+    RG_CHECK_ARG(opt != nullptr, "opt is NULL");
+    RG_CHECK_ARG(opt->exp_avg && opt->exp_avg_sq && opt->step >= 1, "an optimizer buffer is NULL or step < 1");
+    return c5_launch_grad(ring, b, (float*)b->params, opt->exp_avg, opt->exp_avg_sq, rg_adam_host(opt->step, opt->lr, opt->beta1, opt->beta2, opt->eps), 1, (hipStream_t)stream);
 }

@@ -14,10 +14,9 @@
 // All arithmetic on the VALU in fp32 with the chains of the header (the chains are what the f32 MFMA forms compute, so a matrix-core version keeps the bits);
 // no floating-point atomics.  Uses mi_common.h read-only for the device helpers; none of its host-side macros (they call into libmirl.so).
 #include "mi_common.h"
+#include "mi_ring.h"
 
 #include "../../include/mi_iqn.h"
-
-#include <stdarg.h>
 
 #define IQ_E MI_IQN_EMB
 #define IQ_H MI_IQN_HID
@@ -36,44 +35,19 @@
 #define IQ_QW2 MI_IQN_QW2
 #define IQ_QB2 MI_IQN_QB2
 #define IQ_BLK 32              // hidden units per backward block (8 per wave)
-#define IQ_STREAM_EXPLORE 3u
-#define IQ_STREAM_SAMPLE 4u
 #define IQ_STREAM_ACT_TAU 9u
 #define IQ_STREAM_TAU 10u
 #define IQ_STREAM_NEXT_TAU 11u
 #define IQ_STREAM_TAU_DASH 12u
-
-// ---- error plumbing of this library ----------------------------------------------------------------
-static thread_local char iq_err[512] = "";
-static void iq_set_error(const char* fmt, ...) {
-    va_list ap;
-    va_start(ap, fmt);
-    vsnprintf(iq_err, sizeof(iq_err), fmt, ap);
-    va_end(ap);
-}
-#define IQ_CHECK_ARG(cond, msg)                                       \
-    do {                                                              \
-        if (!(cond)) {                                                \
-            iq_set_error("%s: invalid argument: %s", __func__, msg);  \
-            return MI_IQN_EINVAL;                                     \
-        }                                                             \
-    } while (0)
-#define IQ_HIP(call)                                                                      \
-    do {                                                                                  \
-        hipError_t e_ = (call);                                                           \
-        if (e_ != hipSuccess) {                                                           \
-            iq_set_error("%s: %s failed: %s", __func__, #call, hipGetErrorString(e_));    \
-            return MI_IQN_EHIP;                                                           \
-        }                                                                                 \
-    } while (0)
+static_assert(MI_IQN_OK == RG_OK && MI_IQN_EINVAL == RG_EINVAL && MI_IQN_EHIP == RG_EHIP && MI_IQN_MAX_STEPS_PER_CALL == RG_MAX_STEPS, "mi_ring.h returns these");
 
 #ifndef MI_IQN_SOURCE_ID
 #define MI_IQN_SOURCE_ID "unknown"
 #endif
 extern "C" int mi_iqn_version(void) { return MI_IQN_VERSION; }
-extern "C" const char* mi_iqn_last_error(void) { return iq_err; }
+extern "C" const char* mi_iqn_last_error(void) { return rg_err; }
 extern "C" const char* mi_iqn_source_id(void) { return MI_IQN_SOURCE_ID; }
-static int iq_slabs(int batch) { return batch < MI_IQN_MAX_SLABS ? batch : MI_IQN_MAX_SLABS; }
+static int iq_slabs(int batch) { return rg_slabs(batch, MI_IQN_MAX_SLABS); }
 extern "C" size_t mi_iqn_workspace_bytes(int batch) {
     if (batch <= 0) return 0;
     return (size_t)iq_slabs(batch) * IQ_STRIDE * sizeof(float);
@@ -224,112 +198,45 @@ __global__ void __launch_bounds__(256) iqn_forward_kernel(const float* __restric
 // =====================================================================================================
 // acting
 // =====================================================================================================
-struct iq_eps_tab { double v[MI_IQN_MAX_STEPS_PER_CALL]; };   // epsilon(global_step + k) in the reference's double arithmetic, passed by value
+// the greedy action of rg_act_loop: the step's 32 taus (drawn or forced, reported through taus_out), then the mean of their quantiles
+template <bool FORCED>
+struct iq_policy {
+    const float* __restrict__ params;
+    const float* forced_taus;
+    float* taus_out;
+    uint64_t seed;
+    int N;
+    iq_smem& sm;
+    int t, lane, c;
+    __device__ __forceinline__ int greedy(const float4& x, int s, int n, uint64_t env_id, uint64_t ctr) {
+        const int j = lane & 31;
+        const float tau = (FORCED && forced_taus) ? forced_taus[((size_t)s * N + n) * MI_IQN_N_QUANT + j]
+                                                  : iq_tau_draw(seed, env_id, ctr * 8 + (uint64_t)(j >> 2), j & 3, IQ_STREAM_ACT_TAU);
+        if (taus_out && t < MI_IQN_N_QUANT) taus_out[((size_t)s * N + n) * MI_IQN_N_QUANT + t] = tau;
+        iq_features(params, x, sm, t);
+        iq_tau_embed(params, tau, sm, lane, c);
+        float prod[64];
+        iq_load_prod(sm, lane, prod);
+        iq_head(params, prod, sm, t, lane, c);
+        iq_mean(sm, MI_IQN_N_QUANT, t);
+        const int a = sm.q[1] > sm.q[0] ? 1 : 0;   // torch.argmax: the first index on a tie
+        __syncthreads();
+        return a;
+    }
+};
 
 template <bool FORCED>
-__global__ void __launch_bounds__(256) iqn_act_kernel(mi_env e, mi_iqn_ring_t ring, mi_iqn_act_t a_, iq_eps_tab eps) {
+__global__ void __launch_bounds__(256) iqn_act_kernel(mi_env e, mi_iqn_ring_t ring, mi_iqn_act_t a_, rg_eps_tab eps) {
     __shared__ iq_smem sm;
     const int t = threadIdx.x, lane = t & 63, c = __builtin_amdgcn_readfirstlane(t >> 6);
-    const int N = e.n;
-    const long long slots = ring.slots;
-    const float* __restrict__ params = a_.params;
-    int st_cnt = 0, st_len = 0, st_max = 0;
-    for (int n = blockIdx.x; n < N; n += gridDim.x) {
-        // the env's state lives in every thread's registers (uniform across the workgroup); thread 0 does the stores
-        const uint64_t env_id = e.env_id_base + (uint64_t)n;
-        double s0 = e.x[n], s1 = e.x_dot[n], s2 = e.theta[n], s3 = e.theta_dot[n];
-        int elapsed = e.elapsed[n], eplen = e.ep_len[n];
-        float epret = e.ep_ret[n];
-        uint64_t episode = e.episode[n], ctr = e.step_ctr[n];
-        float4 x = reinterpret_cast<const float4*>(a_.obs_cur)[n];
-        // every wave holds env n's state before thread 0 may store the advanced one below (a chunk of exploring steps has no other barrier)
-        __syncthreads();
-        long long slot = a_.global_step % slots;
-        for (int s = 0; s < a_.n_steps; ++s) {
-            int a;
-            if (FORCED && a_.forced_actions) {
-                a = a_.forced_actions[(size_t)s * N + n] != 0 ? 1 : 0;
-            } else {
-                uint32_t r[4];
-                mi_philox(e.seed, env_id, ctr, IQ_STREAM_EXPLORE, r);
-                if (a_.global_step + s < a_.learning_starts || (double)mi_u32_to_uniform(r[0]) < eps.v[s]) {
-                    a = (int)(r[1] & 1u);
-                } else {   // uniform branch: the whole workgroup works on this env
-                    const int j = lane & 31;
-                    const float tau = (FORCED && a_.forced_taus) ? a_.forced_taus[((size_t)s * N + n) * MI_IQN_N_QUANT + j]
-                                                                 : iq_tau_draw(e.seed, env_id, ctr * 8 + (uint64_t)(j >> 2), j & 3, IQ_STREAM_ACT_TAU);
-                    if (a_.taus_out && t < MI_IQN_N_QUANT) a_.taus_out[((size_t)s * N + n) * MI_IQN_N_QUANT + t] = tau;
-                    iq_features(params, x, sm, t);
-                    iq_tau_embed(params, tau, sm, lane, c);
-                    float prod[64];
-                    iq_load_prod(sm, lane, prod);
-                    iq_head(params, prod, sm, t, lane, c);
-                    iq_mean(sm, MI_IQN_N_QUANT, t);
-                    a = sm.q[1] > sm.q[0] ? 1 : 0;   // torch.argmax: the first index on a tie
-                    __syncthreads();
-                }
-            }
-            int term;
-            mi_cartpole_step(s0, s1, s2, s3, a, term);
-            elapsed += 1; eplen += 1; epret += 1.0f;
-            const bool trunc = !term && elapsed >= CP_MAX_STEPS;
-            const bool done = term || trunc;
-            const int fin_len = eplen; const float fin_ret = epret;
-            if (done) {
-                double rs[4];
-                if (FORCED && a_.forced_resets) {
-#pragma unroll
-                    for (int k = 0; k < 4; ++k) rs[k] = a_.forced_resets[4 * ((size_t)s * N + n) + k];
-                } else {
-                    mi_reset_noise(e.seed, env_id, episode, rs);
-                }
-                episode += 1;
-                s0 = rs[0]; s1 = rs[1]; s2 = rs[2]; s3 = rs[3];
-                elapsed = 0; eplen = 0; epret = 0.0f;
-            }
-            x = make_float4((float)s0, (float)s1, (float)s2, (float)s3);
-            const long long nslot = slot + 1 == slots ? 0 : slot + 1;
-            if (t == 0) {
-                ring.actions[slot * N + n] = a;
-                reinterpret_cast<float4*>(ring.observations)[nslot * N + n] = x;
-                ring.rewards[nslot * N + n] = 1.0f;
-                ring.terminated[nslot * N + n] = (uint8_t)(term ? 1 : 0);
-                if (done) {
-                    st_cnt += 1; st_len += fin_len; st_max = fin_len > st_max ? fin_len : st_max;
-                    if (a_.episode_stats && a_.max_ep > 0) {
-                        const int sl = atomicAdd(a_.episode_stats + 3, 1);
-                        if (sl < a_.max_ep) a_.episodes[sl] = mi_episode_t{n, s, fin_ret, fin_len};
-                    }
-                }
-            }
-            slot = nslot;
-            ctr += 1;
-        }
-        if (t == 0) {
-            e.x[n] = s0; e.x_dot[n] = s1; e.theta[n] = s2; e.theta_dot[n] = s3;
-            e.elapsed[n] = elapsed; e.ep_ret[n] = epret; e.ep_len[n] = eplen; e.episode[n] = episode; e.step_ctr[n] = ctr;
-            reinterpret_cast<float4*>(a_.obs_cur)[n] = x;
-        }
-    }
-    if (t == 0 && a_.episode_stats && st_cnt > 0) { atomicAdd(a_.episode_stats, st_cnt); atomicAdd(a_.episode_stats + 1, st_len); atomicMax(a_.episode_stats + 2, st_max); }
+    iq_policy<FORCED> policy{a_.params, a_.forced_taus, a_.taus_out, e.seed, e.n, sm, t, lane, c};
+    const rg_act_args a{a_.obs_cur, a_.forced_actions, a_.forced_resets, a_.episodes, a_.episode_stats, a_.global_step, a_.learning_starts, a_.n_steps, a_.max_ep};
+    rg_act_loop<FORCED>(e, ring, a, eps, policy);
 }
 
 // =====================================================================================================
 // targets, loss, gradient
 // =====================================================================================================
-__device__ __forceinline__ long long iq_row_index(const mi_iqn_batch_t& bt, int b, long long total, int t, bool store) {
-    long long i;
-    if (bt.sample_upper > 0) {
-        uint32_t r[4];
-        mi_philox(bt.seed, bt.update, (uint64_t)b, IQ_STREAM_SAMPLE, r);
-        i = (long long)((((uint64_t)r[1] << 32) | r[0]) % (uint64_t)bt.sample_upper);
-        if (store && t == 0) bt.idx[b] = i;
-    } else {
-        i = bt.idx[b];
-    }
-    return i < 0 ? 0 : (i >= total ? total - 1 : i);   // a bad index reads a valid row, never past the ring
-}
-
 // next_actions[b] and target[b][:] of ring row i from the target networks TP; sm.tgt valid for every thread on return
 __device__ __forceinline__ void iq_target_row(const float* __restrict__ TP, const mi_iqn_ring_t& ring, const mi_iqn_batch_t& bt, int b, long long i, iq_smem& sm, int t,
                                               int lane, int c) {
@@ -440,7 +347,7 @@ __global__ void __launch_bounds__(256) iqn_grad_kernel(mi_iqn_ring_t ring, mi_iq
     __syncthreads();
     float (*X)[64] = reinterpret_cast<float (*)[64]>(&sm.blk[0][0][0]);   // dprod[e][i] once the block loop is over
     for (int b = blockIdx.x; b < bt.batch; b += gridDim.x) {
-        const long long i = iq_row_index(bt, b, total, t, true);
+        const long long i = rg_row_index(bt.seed, bt.update, bt.sample_upper, bt.idx, b, total, t == 0);
         // ---- targets, with the target networks ----
         iq_target_row(bt.target_params, ring, bt, b, i, sm, t, lane, c);
         // ---- online forward ----
@@ -599,150 +506,99 @@ __global__ void __launch_bounds__(256) iqn_grad_kernel(mi_iqn_ring_t ring, mi_iq
     }
 }
 
-struct iq_adam_consts { float w1, b2, w2, step_size, rbc2, eps; };
-// the host-side coefficients exactly as libmirl's mi_adam forms them
-static iq_adam_consts iq_adam_host(int64_t step, double lr, double beta1, double beta2, double eps) {
-    const double bc1 = 1.0 - pow(beta1, (double)step), bc2 = 1.0 - pow(beta2, (double)step);
-    iq_adam_consts k;
-    k.w1 = (float)(1.0 - beta1); k.b2 = (float)beta2; k.w2 = (float)(1.0 - beta2);
-    k.step_size = (float)(lr / bc1); k.rbc2 = (float)(1.0 / sqrt(bc2)); k.eps = (float)eps;
-    return k;
-}
-
-// 32 elements x 16 slab groups per workgroup: thread (j, k) adds the slabs g = k, k + 16, ... of element j in ascending g on four interleaved accumulators, the 16
-// group sums are then added in ascending k.  Element MI_IQN_NPARAMS is the sum of the row losses.
-#define IQ_RED_GROUPS 16
-__global__ void __launch_bounds__(32 * IQ_RED_GROUPS) iqn_reduce_kernel(const float* __restrict__ slabs, int n_slabs, float inv, float* __restrict__ grads,
+__global__ void __launch_bounds__(32 * RG_RED_GROUPS) iqn_reduce_kernel(const float* __restrict__ slabs, int n_slabs, float inv, float* __restrict__ grads,
                                                                          float* __restrict__ loss, float* __restrict__ p, float* __restrict__ m, float* __restrict__ v,
-                                                                         iq_adam_consts k, int adam) {
-    __shared__ float part[IQ_RED_GROUPS][32];
-    const int j = threadIdx.x & 31, grp = threadIdx.x >> 5;
-    const int i = blockIdx.x * 32 + j;
-    float s0 = 0.0f, s1 = 0.0f, s2 = 0.0f, s3 = 0.0f;
-    if (i <= IQ_NP) {
-        int g = grp;
-        for (; g + 3 * IQ_RED_GROUPS < n_slabs; g += 4 * IQ_RED_GROUPS) {
-            s0 += slabs[(size_t)(g + 0 * IQ_RED_GROUPS) * IQ_STRIDE + i]; s1 += slabs[(size_t)(g + 1 * IQ_RED_GROUPS) * IQ_STRIDE + i];
-            s2 += slabs[(size_t)(g + 2 * IQ_RED_GROUPS) * IQ_STRIDE + i]; s3 += slabs[(size_t)(g + 3 * IQ_RED_GROUPS) * IQ_STRIDE + i];
-        }
-        if (g < n_slabs) s0 += slabs[(size_t)g * IQ_STRIDE + i];
-        if (g + IQ_RED_GROUPS < n_slabs) s1 += slabs[(size_t)(g + IQ_RED_GROUPS) * IQ_STRIDE + i];
-        if (g + 2 * IQ_RED_GROUPS < n_slabs) s2 += slabs[(size_t)(g + 2 * IQ_RED_GROUPS) * IQ_STRIDE + i];
-    }
-    part[grp][j] = (s0 + s1) + (s2 + s3);
-    __syncthreads();
-    if (grp != 0 || i > IQ_NP) return;
-    float sum = part[0][j];
-#pragma unroll
-    for (int q = 1; q < IQ_RED_GROUPS; ++q) sum += part[q][j];
-    if (i == IQ_NP) { loss[0] = sum * inv; return; }
-    grads[i] = sum;
-    if (adam) {
-        float mi = m[i], vi = v[i];
-        p[i] = mi_adam_elem(p[i], sum, mi, vi, k.w1, k.b2, k.w2, k.step_size, k.rbc2, k.eps);
-        m[i] = mi; v[i] = vi;
-    }
+                                                                         rg_adam_consts k, int adam) {
+    rg_reduce<IQ_NP, IQ_STRIDE>(slabs, n_slabs, inv, grads, loss, p, m, v, k, adam);
 }
 
 // ---- C ABI -------------------------------------------------------------------------------------------
-static bool iq_aligned(const void* p) { return ((uintptr_t)p & 15u) == 0; }   // parameters, observations and slabs are read and written as float4
-static int iq_check_ring(const mi_iqn_ring_t* r) {
-    IQ_CHECK_ARG(r != nullptr, "ring is NULL");
-    IQ_CHECK_ARG(r->observations && r->actions && r->rewards && r->terminated, "a ring buffer is NULL");
-    IQ_CHECK_ARG(r->slots >= 2 && r->n_envs >= 1, "slots must be >= 2 and n_envs >= 1");
-    IQ_CHECK_ARG(iq_aligned(r->observations), "observations must be 16-byte aligned");
-    return MI_IQN_OK;
-}
-
 extern "C" int mi_iqn_forward(const float* params, const float* obs, const float* taus, int n, int k, float* quantiles, float* q, void* stream) {
-    IQ_CHECK_ARG(params && obs && taus && n > 0 && (quantiles || q), "bad arguments");
-    IQ_CHECK_ARG(k >= 1 && k <= MI_IQN_N_TAU, "k must be in [1, 64]");
-    IQ_CHECK_ARG(iq_aligned(params) && iq_aligned(obs), "params and obs must be 16-byte aligned");
+    RG_CHECK_ARG(params && obs && taus && n > 0 && (quantiles || q), "bad arguments");
+    RG_CHECK_ARG(k >= 1 && k <= MI_IQN_N_TAU, "k must be in [1, 64]");
+    RG_CHECK_ARG(rg_aligned(params) && rg_aligned(obs), "params and obs must be 16-byte aligned");
     iqn_forward_kernel<<<n < 1024 ? n : 1024, 256, 0, (hipStream_t)stream>>>(params, obs, taus, n, k, quantiles, q);
-    IQ_HIP(hipGetLastError());
+    RG_HIP(hipGetLastError());
     return MI_IQN_OK;
 }
 
 extern "C" int mi_iqn_act_steps(void* handle, const mi_iqn_ring_t* ring, const mi_iqn_act_t* a, void* stream) {
     const mi_env* e = (const mi_env*)handle;
-    IQ_CHECK_ARG(e != nullptr && a != nullptr, "NULL pointer");
-    IQ_CHECK_ARG(a->params && a->obs_cur, "params or obs_cur is NULL");
-    IQ_CHECK_ARG(iq_aligned(a->params) && iq_aligned(a->obs_cur), "params and obs_cur must be 16-byte aligned");
-    const int rc = iq_check_ring(ring);
+    RG_CHECK_ARG(e != nullptr && a != nullptr, "NULL pointer");
+    RG_CHECK_ARG(a->params && a->obs_cur, "params or obs_cur is NULL");
+    RG_CHECK_ARG(rg_aligned(a->params) && rg_aligned(a->obs_cur), "params and obs_cur must be 16-byte aligned");
+    const int rc = rg_check_ring(ring);
     if (rc != MI_IQN_OK) return rc;
-    IQ_CHECK_ARG(e->kind == MI_ENV_CARTPOLE_V1 && e->n > 0, "env is not a CartPole-v1 handle");
-    IQ_CHECK_ARG(e->n == ring->n_envs, "the ring's n_envs is not the handle's");
-    IQ_CHECK_ARG(a->n_steps > 0 && a->n_steps <= MI_IQN_MAX_STEPS_PER_CALL, "n_steps must be in [1, 64]");
-    IQ_CHECK_ARG(a->global_step >= 0 && a->learning_starts >= 0, "global_step < 0 or learning_starts < 0");
-    IQ_CHECK_ARG(a->max_ep >= 0 && (a->max_ep == 0 || (a->episodes && a->episode_stats)), "episodes / episode_stats buffer missing");
+    RG_CHECK_ARG(e->kind == MI_ENV_CARTPOLE_V1 && e->n > 0, "env is not a CartPole-v1 handle");
+    RG_CHECK_ARG(e->n == ring->n_envs, "the ring's n_envs is not the handle's");
+    RG_CHECK_ARG(a->n_steps > 0 && a->n_steps <= MI_IQN_MAX_STEPS_PER_CALL, "n_steps must be in [1, 64]");
+    RG_CHECK_ARG(a->global_step >= 0 && a->learning_starts >= 0, "global_step < 0 or learning_starts < 0");
+    RG_CHECK_ARG(a->max_ep >= 0 && (a->max_ep == 0 || (a->episodes && a->episode_stats)), "episodes / episode_stats buffer missing");
     hipStream_t s = (hipStream_t)stream;
-    iq_eps_tab tab;
-    for (int k = 0; k < MI_IQN_MAX_STEPS_PER_CALL; ++k) {
-        const double ev = 1.0 + a->slope * (double)(a->global_step + k);
-        tab.v[k] = ev > a->final_epsilon ? ev : a->final_epsilon;
-    }
-    if (a->episode_stats) IQ_HIP(hipMemsetAsync(a->episode_stats, 0, 4 * sizeof(int32_t), s));
+    rg_eps_tab tab;
+    rg_eps_fill(tab, a->global_step, a->slope, 1.0, a->final_epsilon);   // epsilon = max(1 + slope * step, final_epsilon)
+    if (a->episode_stats) RG_HIP(hipMemsetAsync(a->episode_stats, 0, 4 * sizeof(int32_t), s));
     const int grid = e->n < 1024 ? e->n : 1024;
     if (a->forced_actions || a->forced_resets || a->forced_taus)
         iqn_act_kernel<true><<<grid, 256, 0, s>>>(*e, *ring, *a, tab);
     else
         iqn_act_kernel<false><<<grid, 256, 0, s>>>(*e, *ring, *a, tab);
-    IQ_HIP(hipGetLastError());
+    RG_HIP(hipGetLastError());
     return MI_IQN_OK;
 }
 
 extern "C" int mi_iqn_target(const mi_iqn_ring_t* ring, const mi_iqn_batch_t* b, void* stream) {
-    const int rc = iq_check_ring(ring);
+    const int rc = rg_check_ring(ring);
     if (rc != MI_IQN_OK) return rc;
-    IQ_CHECK_ARG(b != nullptr, "batch is NULL");
-    IQ_CHECK_ARG(b->batch > 0, "batch <= 0");
-    IQ_CHECK_ARG(b->target_params && b->idx && b->next_actions && b->target, "a batch buffer is NULL");
-    IQ_CHECK_ARG(iq_aligned(b->target_params), "target_params must be 16-byte aligned");
+    RG_CHECK_ARG(b != nullptr, "batch is NULL");
+    RG_CHECK_ARG(b->batch > 0, "batch <= 0");
+    RG_CHECK_ARG(b->target_params && b->idx && b->next_actions && b->target, "a batch buffer is NULL");
+    RG_CHECK_ARG(rg_aligned(b->target_params), "target_params must be 16-byte aligned");
     iqn_target_kernel<<<b->batch < 1024 ? b->batch : 1024, 256, 0, (hipStream_t)stream>>>(*ring, *b);
-    IQ_HIP(hipGetLastError());
+    RG_HIP(hipGetLastError());
     return MI_IQN_OK;
 }
 
 extern "C" int mi_iqn_quantile_huber(const float* current, const float* target, const float* taus, int batch, float* loss, float* dcurrent, void* stream) {
-    IQ_CHECK_ARG(current && target && taus && loss && dcurrent, "NULL pointer");
-    IQ_CHECK_ARG(batch > 0 && batch <= (1 << 24), "batch must be in [1, 2^24]");
+    RG_CHECK_ARG(current && target && taus && loss && dcurrent, "NULL pointer");
+    RG_CHECK_ARG(batch > 0 && batch <= (1 << 24), "batch must be in [1, 2^24]");
     iqn_huber_kernel<<<1, 256, 0, (hipStream_t)stream>>>(current, target, taus, batch, loss, dcurrent);
-    IQ_HIP(hipGetLastError());
+    RG_HIP(hipGetLastError());
     return MI_IQN_OK;
 }
 
 static int iq_check_batch(const mi_iqn_ring_t* ring, const mi_iqn_batch_t* b) {
-    const int rc = iq_check_ring(ring);
+    const int rc = rg_check_ring(ring);
     if (rc != MI_IQN_OK) return rc;
-    IQ_CHECK_ARG(b != nullptr, "batch is NULL");
-    IQ_CHECK_ARG(b->batch > 0 && b->batch <= (1 << 24), "batch must be in [1, 2^24]");
-    IQ_CHECK_ARG(b->params && b->target_params && b->idx && b->taus && b->current && b->target && b->next_actions && b->grads && b->loss && b->workspace,
+    RG_CHECK_ARG(b != nullptr, "batch is NULL");
+    RG_CHECK_ARG(b->batch > 0 && b->batch <= (1 << 24), "batch must be in [1, 2^24]");
+    RG_CHECK_ARG(b->params && b->target_params && b->idx && b->taus && b->current && b->target && b->next_actions && b->grads && b->loss && b->workspace,
                  "a batch buffer is NULL");
-    IQ_CHECK_ARG(iq_aligned(b->params) && iq_aligned(b->target_params) && iq_aligned(b->workspace), "params, target_params and workspace must be 16-byte aligned");
-    IQ_CHECK_ARG(b->sample_upper >= 0 && b->sample_upper <= ring->slots * (int64_t)ring->n_envs, "sample_upper outside [0, slots * n_envs]");
+    RG_CHECK_ARG(rg_aligned(b->params) && rg_aligned(b->target_params) && rg_aligned(b->workspace), "params, target_params and workspace must be 16-byte aligned");
+    RG_CHECK_ARG(b->sample_upper >= 0 && b->sample_upper <= ring->slots * (int64_t)ring->n_envs, "sample_upper outside [0, slots * n_envs]");
     return MI_IQN_OK;
 }
-static int iq_launch_grad(const mi_iqn_ring_t* ring, const mi_iqn_batch_t* b, float* p, float* m, float* v, const iq_adam_consts& k, int adam, hipStream_t s) {
+static int iq_launch_grad(const mi_iqn_ring_t* ring, const mi_iqn_batch_t* b, float* p, float* m, float* v, const rg_adam_consts& k, int adam, hipStream_t s) {
     const int slabs = iq_slabs(b->batch);
     iqn_grad_kernel<<<slabs, 256, 0, s>>>(*ring, *b, (float*)b->workspace);
-    IQ_HIP(hipGetLastError());
-    if (b->mid_event) IQ_HIP(hipEventRecord((hipEvent_t)b->mid_event, s));
-    iqn_reduce_kernel<<<(IQ_NP + 1 + 31) / 32, 32 * IQ_RED_GROUPS, 0, s>>>((const float*)b->workspace, slabs, 1.0f / (float)(b->batch * 64), b->grads, b->loss, p, m, v, k,
+    RG_HIP(hipGetLastError());
+    if (b->mid_event) RG_HIP(hipEventRecord((hipEvent_t)b->mid_event, s));
+    iqn_reduce_kernel<<<(IQ_NP + 1 + 31) / 32, 32 * RG_RED_GROUPS, 0, s>>>((const float*)b->workspace, slabs, 1.0f / (float)(b->batch * 64), b->grads, b->loss, p, m, v, k,
                                                                            adam);
-    IQ_HIP(hipGetLastError());
+    RG_HIP(hipGetLastError());
     return MI_IQN_OK;
 }
 
 extern "C" int mi_iqn_grad(const mi_iqn_ring_t* ring, const mi_iqn_batch_t* b, void* stream) {
     const int rc = iq_check_batch(ring, b);
     if (rc != MI_IQN_OK) return rc;
-    return iq_launch_grad(ring, b, nullptr, nullptr, nullptr, iq_adam_consts{}, 0, (hipStream_t)stream);
+    return iq_launch_grad(ring, b, nullptr, nullptr, nullptr, rg_adam_consts{}, 0, (hipStream_t)stream);
 }
 
 extern "C" int mi_iqn_update(const mi_iqn_ring_t* ring, const mi_iqn_batch_t* b, const mi_iqn_adam_t* opt, void* stream) {
     const int rc = iq_check_batch(ring, b);
     if (rc != MI_IQN_OK) return rc;
-    IQ_CHECK_ARG(opt != nullptr, "opt is NULL");
-    IQ_CHECK_ARG(opt->exp_avg && opt->exp_avg_sq && opt->step >= 1, "an optimizer buffer is NULL or step < 1");
-    return iq_launch_grad(ring, b, (float*)b->params, opt->exp_avg, opt->exp_avg_sq, iq_adam_host(opt->step, opt->lr, opt->beta1, opt->beta2, opt->eps), 1, (hipStream_t)stream);
+    RG_CHECK_ARG(opt != nullptr, "opt is NULL");
+    RG_CHECK_ARG(opt->exp_avg && opt->exp_avg_sq && opt->step >= 1, "an optimizer buffer is NULL or step < 1");
+    return iq_launch_grad(ring, b, (float*)b->params, opt->exp_avg, opt->exp_avg_sq, rg_adam_host(opt->step, opt->lr, opt->beta1, opt->beta2, opt->eps), 1, (hipStream_t)stream);
 }

@@ -13,10 +13,9 @@
 // All arithmetic on the VALU in fp32 with the summation orders of the header; no floating-point atomics.
 // Uses mi_common.h read-only for the device helpers; none of its host-side macros (they call into libmirl.so).
 #include "mi_common.h"
+#include "mi_ring.h"
 
 #include "../../include/mi_qr.h"
-
-#include <stdarg.h>
 
 #define QR_H1 MI_QR_H1
 #define QR_H2 MI_QR_H2
@@ -32,40 +31,15 @@
 #define QR_STRIDE MI_QR_SLAB_STRIDE
 #define QR_W2C 40              // columns of W2 per thread (three threads per row)
 #define QR_DH2C 22             // quantiles per partial chain of dh2 (three threads per column: 22, 22, 20)
-#define QR_STREAM_EXPLORE 3u
-#define QR_STREAM_SAMPLE 4u
-
-// ---- error plumbing of this library ----------------------------------------------------------------
-static thread_local char qr_err[512] = "";
-static void qr_set_error(const char* fmt, ...) {
-    va_list ap;
-    va_start(ap, fmt);
-    vsnprintf(qr_err, sizeof(qr_err), fmt, ap);
-    va_end(ap);
-}
-#define QR_CHECK_ARG(cond, msg)                                       \
-    do {                                                              \
-        if (!(cond)) {                                                \
-            qr_set_error("%s: invalid argument: %s", __func__, msg);  \
-            return MI_QR_EINVAL;                                      \
-        }                                                             \
-    } while (0)
-#define QR_HIP(call)                                                                      \
-    do {                                                                                  \
-        hipError_t e_ = (call);                                                           \
-        if (e_ != hipSuccess) {                                                           \
-            qr_set_error("%s: %s failed: %s", __func__, #call, hipGetErrorString(e_));    \
-            return MI_QR_EHIP;                                                            \
-        }                                                                                 \
-    } while (0)
+static_assert(MI_QR_OK == RG_OK && MI_QR_EINVAL == RG_EINVAL && MI_QR_EHIP == RG_EHIP && MI_QR_MAX_STEPS_PER_CALL == RG_MAX_STEPS, "mi_ring.h returns these");
 
 #ifndef MI_QR_SOURCE_ID
 #define MI_QR_SOURCE_ID "unknown"
 #endif
 extern "C" int mi_qr_version(void) { return MI_QR_VERSION; }
-extern "C" const char* mi_qr_last_error(void) { return qr_err; }
+extern "C" const char* mi_qr_last_error(void) { return rg_err; }
 extern "C" const char* mi_qr_source_id(void) { return MI_QR_SOURCE_ID; }
-static int qr_slabs(int batch) { return batch < MI_QR_MAX_SLABS ? batch : MI_QR_MAX_SLABS; }
+static int qr_slabs(int batch) { return rg_slabs(batch, MI_QR_MAX_SLABS); }
 extern "C" size_t mi_qr_workspace_bytes(int batch) {
     if (batch <= 0) return 0;
     return (size_t)qr_slabs(batch) * QR_STRIDE * sizeof(float);
@@ -201,102 +175,40 @@ __global__ void __launch_bounds__(256) qr_forward_kernel(const float* __restrict
 // =====================================================================================================
 // acting
 // =====================================================================================================
-struct qr_eps_tab { double v[MI_QR_MAX_STEPS_PER_CALL]; };   // epsilon(global_step + k) in double arithmetic, passed by value
+// the greedy action of rg_act_loop: the torso in `w`, the collapsed head in every thread's registers
+struct qr_policy {
+    const qr_torso& w;
+    const float (&wb0)[QR_H2], (&wb1)[QR_H2];
+    float bb0, bb1;
+    qr_smem& sm;
+    int t;
+    __device__ __forceinline__ int greedy(const float4& x, int, int, uint64_t, uint64_t) {
+        qr_torso_row(w, x, sm, t);
+        float q0 = bb0, q1 = bb1;
+#pragma unroll
+        for (int k = 0; k < QR_H2; ++k) {
+            const float h = sm.h2[k];
+            q0 = __builtin_fmaf(wb0[k], h, q0);
+            q1 = __builtin_fmaf(wb1[k], h, q1);
+        }
+        // no barrier here: sm.h2 is next written behind two barriers of the next qr_torso_row, which no wave passes before all have read it
+        return q1 > q0 ? 1 : 0;   // torch.argmax: the first index on a tie
+    }
+};
 
 template <bool FORCED>
-__global__ void __launch_bounds__(256) qr_act_kernel(mi_env e, mi_qr_ring_t ring, mi_qr_act_t a_, qr_eps_tab eps) {
+__global__ void __launch_bounds__(256) qr_act_kernel(mi_env e, mi_qr_ring_t ring, mi_qr_act_t a_, rg_eps_tab eps) {
     __shared__ qr_smem sm;
     const int t = threadIdx.x;
-    const int N = e.n;
-    const long long slots = ring.slots;
-    const int n_steps = a_.n_steps;
     qr_torso w;
     qr_load_torso(w, a_.params, t);
     qr_collapse(a_.params, sm, t);
     float wb0[QR_H2], wb1[QR_H2];   // the collapsed head in every thread's registers
 #pragma unroll
     for (int k = 0; k < QR_H2; ++k) { wb0[k] = sm.wbar[0][k]; wb1[k] = sm.wbar[1][k]; }
-    const float bb0 = sm.bbar[0], bb1 = sm.bbar[1];
-    int st_cnt = 0, st_len = 0, st_max = 0;
-    for (int n = blockIdx.x; n < N; n += gridDim.x) {
-        // the env's state lives in every thread's registers (uniform across the workgroup); thread 0 does the stores
-        const uint64_t env_id = e.env_id_base + (uint64_t)n;
-        double s0 = e.x[n], s1 = e.x_dot[n], s2 = e.theta[n], s3 = e.theta_dot[n];
-        int elapsed = e.elapsed[n], eplen = e.ep_len[n];
-        float epret = e.ep_ret[n];
-        uint64_t episode = e.episode[n], ctr = e.step_ctr[n];
-        float4 x = reinterpret_cast<const float4*>(a_.obs_cur)[n];
-        // every wave holds env n's state before thread 0 may store the advanced one below: a chunk of exploring or teacher-forced steps has no other barrier, and a
-        // wave that read the advanced step counter would take the greedy branch (and its barriers) apart from the rest of the workgroup
-        __syncthreads();
-        long long slot = a_.global_step % slots;
-        for (int s = 0; s < n_steps; ++s) {
-            int a;
-            if (FORCED && a_.forced_actions) {
-                a = a_.forced_actions[(size_t)s * N + n] != 0 ? 1 : 0;
-            } else {
-                uint32_t r[4];
-                mi_philox(e.seed, env_id, ctr, QR_STREAM_EXPLORE, r);
-                if ((double)mi_u32_to_uniform(r[0]) < eps.v[s]) {
-                    a = (int)(r[1] & 1u);
-                } else {   // uniform branch: the whole workgroup works on this env
-                    qr_torso_row(w, x, sm, t);
-                    float q0 = bb0, q1 = bb1;
-#pragma unroll
-                    for (int k = 0; k < QR_H2; ++k) {
-                        const float h = sm.h2[k];
-                        q0 = __builtin_fmaf(wb0[k], h, q0);
-                        q1 = __builtin_fmaf(wb1[k], h, q1);
-                    }
-                    a = q1 > q0 ? 1 : 0;   // torch.argmax: the first index on a tie
-                    // no barrier here: sm.h2 is next written behind two barriers of the next qr_torso_row, which no wave passes before all have read it
-                }
-            }
-            int term;
-            mi_cartpole_step(s0, s1, s2, s3, a, term);
-            elapsed += 1; eplen += 1; epret += 1.0f;
-            const bool trunc = !term && elapsed >= CP_MAX_STEPS;
-            const bool done = term || trunc;
-            const int fin_len = eplen; const float fin_ret = epret;
-            if (done) {
-                double rs[4];
-                if (FORCED && a_.forced_resets) {
-#pragma unroll
-                    for (int k = 0; k < 4; ++k) rs[k] = a_.forced_resets[4 * ((size_t)s * N + n) + k];
-                } else {
-                    mi_reset_noise(e.seed, env_id, episode, rs);
-                }
-                episode += 1;
-                s0 = rs[0]; s1 = rs[1]; s2 = rs[2]; s3 = rs[3];
-                elapsed = 0; eplen = 0; epret = 0.0f;
-            }
-            x = make_float4((float)s0, (float)s1, (float)s2, (float)s3);
-            const long long nslot = slot + 1 == slots ? 0 : slot + 1;
-            if (t == 0) {
-                ring.actions[slot * N + n] = a;
-                reinterpret_cast<float4*>(ring.observations)[nslot * N + n] = x;
-                ring.rewards[nslot * N + n] = 1.0f;
-                ring.terminated[nslot * N + n] = (uint8_t)(term ? 1 : 0);
-                if (done) {
-                    st_cnt += 1; st_len += fin_len; st_max = fin_len > st_max ? fin_len : st_max;
-                    if (a_.episode_stats && a_.max_ep > 0) {
-                        const int sl = atomicAdd(a_.episode_stats + 3, 1);
-                        if (sl < a_.max_ep) a_.episodes[sl] = mi_episode_t{n, s, fin_ret, fin_len};
-                    }
-                }
-            }
-            slot = nslot;
-            ctr += 1;
-        }
-        if (t == 0) {
-            e.x[n] = s0; e.x_dot[n] = s1; e.theta[n] = s2; e.theta_dot[n] = s3;
-            e.elapsed[n] = elapsed; e.ep_ret[n] = epret; e.ep_len[n] = eplen; e.episode[n] = episode; e.step_ctr[n] = ctr;
-            reinterpret_cast<float4*>(a_.obs_cur)[n] = x;
-        }
-    }
-    if (t == 0 && a_.episode_stats && st_cnt > 0) {
-        atomicAdd(a_.episode_stats, st_cnt); atomicAdd(a_.episode_stats + 1, st_len); atomicMax(a_.episode_stats + 2, st_max);
-    }
+    qr_policy policy{w, wb0, wb1, sm.bbar[0], sm.bbar[1], sm, t};
+    const rg_act_args a{a_.obs_cur, a_.forced_actions, a_.forced_resets, a_.episodes, a_.episode_stats, a_.global_step, 0, a_.n_steps, a_.max_ep};
+    rg_act_loop<FORCED>(e, ring, a, eps, policy);
 }
 
 // =====================================================================================================
@@ -386,18 +298,6 @@ __global__ void __launch_bounds__(256) qr_huber_kernel(const float* __restrict__
     if (t == 0) loss[0] = total * inv;
 }
 
-__device__ __forceinline__ long long qr_row_index(const mi_qr_batch_t& bt, int b, long long total) {
-    long long i;
-    if (bt.sample_upper > 0) {
-        uint32_t r[4];
-        mi_philox(bt.sample_seed, bt.sample_update, (uint64_t)b, QR_STREAM_SAMPLE, r);
-        i = (long long)((((uint64_t)r[1] << 32) | r[0]) % (uint64_t)bt.sample_upper);
-    } else {
-        i = bt.idx[b];
-    }
-    return i < 0 ? 0 : (i >= total ? total - 1 : i);
-}
-
 __global__ void __launch_bounds__(256) qr_grad_kernel(mi_qr_ring_t ring, mi_qr_batch_t bt, float* __restrict__ slabs) {
     __shared__ qr_smem sm;
     const int t = threadIdx.x, lane = t & 63, wv = __builtin_amdgcn_readfirstlane(t >> 6);
@@ -409,8 +309,7 @@ __global__ void __launch_bounds__(256) qr_grad_kernel(mi_qr_ring_t ring, mi_qr_b
     qr_load_head(hd, bt.target_params, t);
     qr_collapse(bt.target_params, sm, t);
     for (int b = blockIdx.x; b < bt.batch; b += gridDim.x) {
-        const long long i = qr_row_index(bt, b, total);
-        if (bt.sample_upper > 0 && t == 0) bt.idx[b] = i;
+        const long long i = rg_row_index(bt.sample_seed, bt.sample_update, bt.sample_upper, bt.idx, b, total, t == 0);
         qr_target_row(w, hd, ring, i, bt.gamma, sm, t, bt.next_actions + b, bt.target + (size_t)b * QR_NQ);
     }
     __threadfence_block();   // pass 2 reads the targets this workgroup wrote (qr_target_row ends in a barrier)
@@ -427,7 +326,7 @@ __global__ void __launch_bounds__(256) qr_grad_kernel(mi_qr_ring_t ring, mi_qr_b
     const float inv = 1.0f / (float)(bt.batch * QR_NQ);
     const float* __restrict__ P = bt.params;
     for (int b = blockIdx.x; b < bt.batch; b += gridDim.x) {
-        const long long i = qr_row_index(bt, b, total);   // recomputed, not re-read
+        const long long i = rg_row_index(bt.sample_seed, bt.sample_update, bt.sample_upper, bt.idx, b, total, false);   // recomputed, not re-read
         const float4 x = reinterpret_cast<const float4*>(ring.observations)[i];
         const int a = ring.actions[i] != 0 ? 1 : 0;
         qr_torso_row(w, x, sm, t);
@@ -504,147 +403,95 @@ __global__ void __launch_bounds__(256) qr_grad_kernel(mi_qr_ring_t ring, mi_qr_b
     if (t == 0) { slab[QR_NP] = loss; slab[QR_NP + 1] = 0.0f; slab[QR_NP + 2] = 0.0f; slab[QR_NP + 3] = 0.0f; }
 }
 
-struct qr_adam_consts { float w1, b2, w2, step_size, rbc2, eps; };
-// the host-side coefficients exactly as libmirl's mi_adam forms them
-static qr_adam_consts qr_adam_host(int64_t step, double lr, double beta1, double beta2, double eps) {
-    const double bc1 = 1.0 - pow(beta1, (double)step), bc2 = 1.0 - pow(beta2, (double)step);
-    qr_adam_consts k;
-    k.w1 = (float)(1.0 - beta1); k.b2 = (float)beta2; k.w2 = (float)(1.0 - beta2);
-    k.step_size = (float)(lr / bc1); k.rbc2 = (float)(1.0 / sqrt(bc2)); k.eps = (float)eps;
-    return k;
-}
-
-// 32 elements x 16 slab groups per workgroup: thread (j, k) adds the slabs g = k, k + 16, ... of element j in ascending g on four interleaved accumulators, the 16
-// group sums are then added in ascending k.  Element MI_QR_NPARAMS is the sum of the row losses.
-#define QR_RED_GROUPS 16
-__global__ void __launch_bounds__(32 * QR_RED_GROUPS) qr_reduce_kernel(const float* __restrict__ slabs, int n_slabs, float inv, float* __restrict__ grads,
+__global__ void __launch_bounds__(32 * RG_RED_GROUPS) qr_reduce_kernel(const float* __restrict__ slabs, int n_slabs, float inv, float* __restrict__ grads,
                                                                         float* __restrict__ loss, float* __restrict__ p, float* __restrict__ m, float* __restrict__ v,
-                                                                        qr_adam_consts k, int adam) {
-    __shared__ float part[QR_RED_GROUPS][32];
-    const int j = threadIdx.x & 31, grp = threadIdx.x >> 5;
-    const int i = blockIdx.x * 32 + j;
-    float s0 = 0.0f, s1 = 0.0f, s2 = 0.0f, s3 = 0.0f;
-    if (i <= QR_NP) {
-        int g = grp;
-        for (; g + 3 * QR_RED_GROUPS < n_slabs; g += 4 * QR_RED_GROUPS) {
-            s0 += slabs[(size_t)(g + 0 * QR_RED_GROUPS) * QR_STRIDE + i]; s1 += slabs[(size_t)(g + 1 * QR_RED_GROUPS) * QR_STRIDE + i];
-            s2 += slabs[(size_t)(g + 2 * QR_RED_GROUPS) * QR_STRIDE + i]; s3 += slabs[(size_t)(g + 3 * QR_RED_GROUPS) * QR_STRIDE + i];
-        }
-        if (g < n_slabs) s0 += slabs[(size_t)g * QR_STRIDE + i];
-        if (g + QR_RED_GROUPS < n_slabs) s1 += slabs[(size_t)(g + QR_RED_GROUPS) * QR_STRIDE + i];
-        if (g + 2 * QR_RED_GROUPS < n_slabs) s2 += slabs[(size_t)(g + 2 * QR_RED_GROUPS) * QR_STRIDE + i];
-    }
-    part[grp][j] = (s0 + s1) + (s2 + s3);
-    __syncthreads();
-    if (grp != 0 || i > QR_NP) return;
-    float sum = part[0][j];
-#pragma unroll
-    for (int q = 1; q < QR_RED_GROUPS; ++q) sum += part[q][j];
-    if (i == QR_NP) { loss[0] = sum * inv; return; }
-    grads[i] = sum;
-    if (adam) {
-        float mi = m[i], vi = v[i];
-        p[i] = mi_adam_elem(p[i], sum, mi, vi, k.w1, k.b2, k.w2, k.step_size, k.rbc2, k.eps);
-        m[i] = mi; v[i] = vi;
-    }
+                                                                        rg_adam_consts k, int adam) {
+    rg_reduce<QR_NP, QR_STRIDE>(slabs, n_slabs, inv, grads, loss, p, m, v, k, adam);
 }
 
 // ---- C ABI -------------------------------------------------------------------------------------------
-static bool qr_aligned(const void* p) { return ((uintptr_t)p & 15u) == 0; }   // parameters, observations and slabs are read and written as float4
-static int qr_check_ring(const mi_qr_ring_t* r) {
-    QR_CHECK_ARG(r != nullptr, "ring is NULL");
-    QR_CHECK_ARG(r->observations && r->actions && r->rewards && r->terminated, "a ring buffer is NULL");
-    QR_CHECK_ARG(r->slots >= 2 && r->n_envs >= 1, "slots must be >= 2 and n_envs >= 1");
-    QR_CHECK_ARG(qr_aligned(r->observations), "observations must be 16-byte aligned");
-    return MI_QR_OK;
-}
-
 extern "C" int mi_qr_forward(const float* params, const float* obs, int n, float* quantiles, float* q, void* stream) {
-    QR_CHECK_ARG(params && obs && n > 0 && (quantiles || q), "bad arguments");
-    QR_CHECK_ARG(qr_aligned(params) && qr_aligned(obs), "params and obs must be 16-byte aligned");
+    RG_CHECK_ARG(params && obs && n > 0 && (quantiles || q), "bad arguments");
+    RG_CHECK_ARG(rg_aligned(params) && rg_aligned(obs), "params and obs must be 16-byte aligned");
     qr_forward_kernel<<<n < 1024 ? n : 1024, 256, 0, (hipStream_t)stream>>>(params, obs, n, quantiles, q);
-    QR_HIP(hipGetLastError());
+    RG_HIP(hipGetLastError());
     return MI_QR_OK;
 }
 
 extern "C" int mi_qr_act_steps(void* handle, const mi_qr_ring_t* ring, const mi_qr_act_t* a, void* stream) {
     const mi_env* e = (const mi_env*)handle;
-    QR_CHECK_ARG(e != nullptr && a != nullptr, "NULL pointer");
-    QR_CHECK_ARG(a->params && a->obs_cur, "params or obs_cur is NULL");
-    QR_CHECK_ARG(qr_aligned(a->params) && qr_aligned(a->obs_cur), "params and obs_cur must be 16-byte aligned");
-    const int rc = qr_check_ring(ring);
+    RG_CHECK_ARG(e != nullptr && a != nullptr, "NULL pointer");
+    RG_CHECK_ARG(a->params && a->obs_cur, "params or obs_cur is NULL");
+    RG_CHECK_ARG(rg_aligned(a->params) && rg_aligned(a->obs_cur), "params and obs_cur must be 16-byte aligned");
+    const int rc = rg_check_ring(ring);
     if (rc != MI_QR_OK) return rc;
-    QR_CHECK_ARG(e->kind == MI_ENV_CARTPOLE_V1 && e->n > 0, "env is not a CartPole-v1 handle");
-    QR_CHECK_ARG(e->n == ring->n_envs, "the ring's n_envs is not the handle's");
-    QR_CHECK_ARG(a->n_steps > 0 && a->n_steps <= MI_QR_MAX_STEPS_PER_CALL, "n_steps must be in [1, 64]");
-    QR_CHECK_ARG(a->global_step >= 0 && a->total_timesteps > 0 && a->exploration_fraction > 0.0, "global_step < 0, total_timesteps <= 0 or exploration_fraction <= 0");
-    QR_CHECK_ARG(a->max_ep >= 0 && (a->max_ep == 0 || (a->episodes && a->episode_stats)), "episodes / episode_stats buffer missing");
+    RG_CHECK_ARG(e->kind == MI_ENV_CARTPOLE_V1 && e->n > 0, "env is not a CartPole-v1 handle");
+    RG_CHECK_ARG(e->n == ring->n_envs, "the ring's n_envs is not the handle's");
+    RG_CHECK_ARG(a->n_steps > 0 && a->n_steps <= MI_QR_MAX_STEPS_PER_CALL, "n_steps must be in [1, 64]");
+    RG_CHECK_ARG(a->global_step >= 0 && a->total_timesteps > 0 && a->exploration_fraction > 0.0, "global_step < 0, total_timesteps <= 0 or exploration_fraction <= 0");
+    RG_CHECK_ARG(a->max_ep >= 0 && (a->max_ep == 0 || (a->episodes && a->episode_stats)), "episodes / episode_stats buffer missing");
     hipStream_t s = (hipStream_t)stream;
-    qr_eps_tab tab;
-    const double slope = (a->end_e - a->start_e) / (a->exploration_fraction * (double)a->total_timesteps);
-    for (int k = 0; k < MI_QR_MAX_STEPS_PER_CALL; ++k) {
-        const double ev = slope * (double)(a->global_step + k) + a->start_e;
-        tab.v[k] = ev > a->end_e ? ev : a->end_e;
-    }
-    if (a->episode_stats) QR_HIP(hipMemsetAsync(a->episode_stats, 0, 4 * sizeof(int32_t), s));
+    rg_eps_tab tab;
+    rg_eps_fill(tab, a->global_step, (a->end_e - a->start_e) / (a->exploration_fraction * (double)a->total_timesteps), a->start_e, a->end_e);
+    if (a->episode_stats) RG_HIP(hipMemsetAsync(a->episode_stats, 0, 4 * sizeof(int32_t), s));
     const int grid = e->n < 1024 ? e->n : 1024;
     if (a->forced_actions || a->forced_resets)
         qr_act_kernel<true><<<grid, 256, 0, s>>>(*e, *ring, *a, tab);
     else
         qr_act_kernel<false><<<grid, 256, 0, s>>>(*e, *ring, *a, tab);
-    QR_HIP(hipGetLastError());
+    RG_HIP(hipGetLastError());
     return MI_QR_OK;
 }
 
 extern "C" int mi_qr_target(const mi_qr_ring_t* ring, const mi_qr_batch_t* b, void* stream) {
-    const int rc = qr_check_ring(ring);
+    const int rc = rg_check_ring(ring);
     if (rc != MI_QR_OK) return rc;
-    QR_CHECK_ARG(b != nullptr, "batch is NULL");
-    QR_CHECK_ARG(b->target_params && b->idx && b->next_actions && b->target && b->batch > 0, "bad arguments");
-    QR_CHECK_ARG(qr_aligned(b->target_params), "target_params must be 16-byte aligned");
+    RG_CHECK_ARG(b != nullptr, "batch is NULL");
+    RG_CHECK_ARG(b->target_params && b->idx && b->next_actions && b->target && b->batch > 0, "bad arguments");
+    RG_CHECK_ARG(rg_aligned(b->target_params), "target_params must be 16-byte aligned");
     qr_target_kernel<<<b->batch < 1024 ? b->batch : 1024, 256, 0, (hipStream_t)stream>>>(*ring, *b);
-    QR_HIP(hipGetLastError());
+    RG_HIP(hipGetLastError());
     return MI_QR_OK;
 }
 
 extern "C" int mi_qr_quantile_huber(const float* current, const float* target, int batch, float* loss, float* dcurrent, void* stream) {
-    QR_CHECK_ARG(current && target && loss && dcurrent && batch > 0, "bad arguments");
+    RG_CHECK_ARG(current && target && loss && dcurrent && batch > 0, "bad arguments");
     qr_huber_kernel<<<1, 256, 0, (hipStream_t)stream>>>(current, target, batch, loss, dcurrent);
-    QR_HIP(hipGetLastError());
+    RG_HIP(hipGetLastError());
     return MI_QR_OK;
 }
 
 static int qr_check_batch(const mi_qr_ring_t* ring, const mi_qr_batch_t* b) {
-    const int rc = qr_check_ring(ring);
+    const int rc = rg_check_ring(ring);
     if (rc != MI_QR_OK) return rc;
-    QR_CHECK_ARG(b != nullptr, "batch is NULL");
-    QR_CHECK_ARG(b->batch > 0, "batch <= 0");
-    QR_CHECK_ARG(b->params && b->target_params && b->idx && b->target && b->next_actions && b->grads && b->loss && b->workspace, "a batch buffer is NULL");
-    QR_CHECK_ARG(qr_aligned(b->params) && qr_aligned(b->target_params) && qr_aligned(b->workspace), "params, target_params and workspace must be 16-byte aligned");
-    QR_CHECK_ARG(b->sample_upper >= 0 && b->sample_upper <= ring->slots * (int64_t)ring->n_envs, "sample_upper outside [0, slots * n_envs]");
+    RG_CHECK_ARG(b != nullptr, "batch is NULL");
+    RG_CHECK_ARG(b->batch > 0, "batch <= 0");
+    RG_CHECK_ARG(b->params && b->target_params && b->idx && b->target && b->next_actions && b->grads && b->loss && b->workspace, "a batch buffer is NULL");
+    RG_CHECK_ARG(rg_aligned(b->params) && rg_aligned(b->target_params) && rg_aligned(b->workspace), "params, target_params and workspace must be 16-byte aligned");
+    RG_CHECK_ARG(b->sample_upper >= 0 && b->sample_upper <= ring->slots * (int64_t)ring->n_envs, "sample_upper outside [0, slots * n_envs]");
     return MI_QR_OK;
 }
-static int qr_launch_grad(const mi_qr_ring_t* ring, const mi_qr_batch_t* b, float* p, float* m, float* v, const qr_adam_consts& k, int adam, hipStream_t s) {
+static int qr_launch_grad(const mi_qr_ring_t* ring, const mi_qr_batch_t* b, float* p, float* m, float* v, const rg_adam_consts& k, int adam, hipStream_t s) {
     const int slabs = qr_slabs(b->batch);
     qr_grad_kernel<<<slabs, 256, 0, s>>>(*ring, *b, (float*)b->workspace);
-    QR_HIP(hipGetLastError());
-    if (b->mid_event) QR_HIP(hipEventRecord((hipEvent_t)b->mid_event, s));
-    qr_reduce_kernel<<<(QR_NP + 1 + 31) / 32, 32 * QR_RED_GROUPS, 0, s>>>((const float*)b->workspace, slabs, 1.0f / (float)(b->batch * QR_NQ), b->grads, b->loss, p, m, v, k,
+    RG_HIP(hipGetLastError());
+    if (b->mid_event) RG_HIP(hipEventRecord((hipEvent_t)b->mid_event, s));
+    qr_reduce_kernel<<<(QR_NP + 1 + 31) / 32, 32 * RG_RED_GROUPS, 0, s>>>((const float*)b->workspace, slabs, 1.0f / (float)(b->batch * QR_NQ), b->grads, b->loss, p, m, v, k,
                                                                         adam);
-    QR_HIP(hipGetLastError());
+    RG_HIP(hipGetLastError());
     return MI_QR_OK;
 }
 
 extern "C" int mi_qr_grad(const mi_qr_ring_t* ring, const mi_qr_batch_t* b, void* stream) {
     const int rc = qr_check_batch(ring, b);
     if (rc != MI_QR_OK) return rc;
-    return qr_launch_grad(ring, b, nullptr, nullptr, nullptr, qr_adam_consts{}, 0, (hipStream_t)stream);
+    return qr_launch_grad(ring, b, nullptr, nullptr, nullptr, rg_adam_consts{}, 0, (hipStream_t)stream);
 }
 
 extern "C" int mi_qr_update(const mi_qr_ring_t* ring, const mi_qr_batch_t* b, const mi_qr_adam_t* opt, void* stream) {
     const int rc = qr_check_batch(ring, b);
     if (rc != MI_QR_OK) return rc;
-    QR_CHECK_ARG(opt != nullptr, "opt is NULL");
-    QR_CHECK_ARG(opt->exp_avg && opt->exp_avg_sq && opt->step >= 1, "an optimizer buffer is NULL or step < 1");
-    return qr_launch_grad(ring, b, (float*)b->params, opt->exp_avg, opt->exp_avg_sq, qr_adam_host(opt->step, opt->lr, opt->beta1, opt->beta2, opt->eps), 1, (hipStream_t)stream);
+    RG_CHECK_ARG(opt != nullptr, "opt is NULL");
+    RG_CHECK_ARG(opt->exp_avg && opt->exp_avg_sq && opt->step >= 1, "an optimizer buffer is NULL or step < 1");
+    return qr_launch_grad(ring, b, (float*)b->params, opt->exp_avg, opt->exp_avg_sq, rg_adam_host(opt->step, opt->lr, opt->beta1, opt->beta2, opt->eps), 1, (hipStream_t)stream);
 }

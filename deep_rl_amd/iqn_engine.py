@@ -1,7 +1,7 @@
-"""IQNEngine — device-resident replay ring + the launch sequence of reference iqn.py:185-299 (re-targeted to CartPole-v1).
+"""IQNEngine — the launch sequence of reference iqn.py:185-299 (re-targeted to CartPole-v1) over libmirl_iqn.so (include/mi_iqn.h).
 
-The surface of C51Engine over libmirl_iqn.so (include/mi_iqn.h): the four replay tensors with the reference's names (iqn.py:174-177) plus an env axis, laid out as a
-[slots, N] time-major ring; methods are thin launch wrappers, nothing is computed in Python.  Single process only.
+The surface of C51Engine: the replay ring and everything around it is RingEngine's (_ring_engine.py); this file adds IQN's epsilon schedule, its tau and quantile
+tensors, the teacher forcing of the taus and the two calls whose arguments are the library's own.
 """
 import ctypes as C
 from types import SimpleNamespace
@@ -9,57 +9,23 @@ from types import SimpleNamespace
 import torch
 
 from . import _native_iqn as K
-from . import dist as D
-from .optim import Adam
+from ._ring_engine import RingEngine
 
 
-class IQNEngine:
+class IQNEngine(RingEngine):
+    K, ALGO, NEEDS = K, "IQN", "two packed IQN parameter buffers of %d floats" % K.NPARAMS
+
     def __init__(self, env, params, target_params, optimizer, slots, batch_size=32, gamma=0.99, final_epsilon=0.01, epsilon_decay_steps=10_000, learning_starts=1_000,
                  max_episodes_logged=None, process_group=None):
         """params / target_params: the packed 44,898-float buffers of the three online / target modules (``pack(features_extractor, cosine_net, quantile_net)``)."""
-        if D.world_size(process_group) > 1:
-            raise K.MiError("IQNEngine runs in a single process (world size %d given): sharding is not built for IQN" % D.world_size(process_group))
-        if tuple(env.observation_space.shape) != (4,) or params.numel() != K.NPARAMS or target_params.numel() != K.NPARAMS:
-            raise K.MiError("IQNEngine needs a CartPole env and two packed IQN parameter buffers of %d floats" % K.NPARAMS)
-        self.env, self.optimizer = env, optimizer
-        self.q, self.target_network = SimpleNamespace(flat=params), SimpleNamespace(flat=target_params)   # (`target` is the method below)
-        self.N, self.device, self.slots = env.num_envs, env.device, int(slots)
-        if self.slots < 2 or int(batch_size) < 1:
-            raise K.MiError("IQNEngine: slots must be >= 2 and batch_size >= 1")
-        self.batch_size, self.gamma = int(batch_size), float(gamma)
+        super().__init__(env, SimpleNamespace(flat=params), SimpleNamespace(flat=target_params), optimizer, slots, batch_size, gamma, max_episodes_logged, process_group)
         self.final_epsilon, self.learning_starts = float(final_epsilon), int(learning_starts)
         self.slope = -(1.0 - self.final_epsilon) / epsilon_decay_steps   # iqn.py:123
-        dev, S, Nn, B = self.device, self.slots, self.N, self.batch_size
-        self.observations = torch.zeros((S, Nn, 4), dtype=torch.float32, device=dev)   # iqn.py:174 (f32: no uint8 storage, no / 255)
-        self.actions = torch.zeros((S, Nn), dtype=torch.int64, device=dev)             # :175
-        self.rewards = torch.zeros((S, Nn), dtype=torch.float32, device=dev)           # :176
-        self.terminated = torch.zeros((S, Nn), dtype=torch.uint8, device=dev)          # :177 (bool)
-        self.batch_inds = torch.zeros(B, dtype=torch.int64, device=dev)
+        dev, B = self.device, self.batch_size
         self.taus = torch.zeros((B, K.N_TAU), dtype=torch.float32, device=dev)
         self.current_action_quantiles = torch.zeros((B, K.N_TAU), dtype=torch.float32, device=dev)
         self.target_action_quantiles = torch.zeros((B, K.N_TAU_PRIME), dtype=torch.float32, device=dev)
-        self.next_actions = torch.zeros(B, dtype=torch.int32, device=dev)
-        self.grads = torch.zeros(K.NPARAMS, dtype=torch.float32, device=dev)
-        self.loss = torch.zeros(1, dtype=torch.float32, device=dev)
-        self.workspace = torch.empty(K.lib().mi_iqn_workspace_bytes(B), dtype=torch.uint8, device=dev)
-        self.max_ep = int(max_episodes_logged if max_episodes_logged is not None else (1024 if Nn <= 8 else 0))
-        self.episodes = torch.zeros((max(self.max_ep, 1), 4), dtype=torch.int32, device=dev)
-        self.episode_stats = torch.zeros(4, dtype=torch.int32, device=dev)
-        self._ring = K.IQNRing(K.ptr(self.observations), K.ptr(self.actions), K.ptr(self.rewards), K.ptr(self.terminated), S, Nn, 0)
-        self.observation = None
-        self.global_step = 0      # time steps taken (each advances every env once)
-        self.update_index = 0
-        self.mid_event = None
         self._forced = (None, None, None)
-
-    def _s(self):
-        return K.stream_ptr(self.device)
-
-    def reset(self, forced_state=None):
-        """observation = env.reset(); observations[global_step % memory_size] = observation (iqn.py:180-182)."""
-        self.observation = self.env.reset(forced_state)
-        self.observations[self.global_step % self.slots].copy_(self.observation)
-        return self.observation
 
     def act(self, n_steps, forced_actions=None, forced_resets=None, forced_taus=None, taus_out=None):
         """n_steps iterations of iqn.py:185-217 for every env, one launch.  taus_out: f32 [n_steps, N, 32] device tensor that receives the taus of the greedy steps."""
@@ -76,33 +42,6 @@ class IQNEngine:
         K.check(K.lib().mi_iqn_act_steps(self.env.handle, C.byref(self._ring), C.byref(a), self._s()), "mi_iqn_act_steps")
         self.global_step += n
 
-    def drain_episodes(self):
-        """Host sync. -> (count, [(env, step_in_call, return, length)] sorted by (step, env)) of the last act() call."""
-        st = self.episode_stats.tolist()
-        k = min(st[3], self.max_ep)
-        if k == 0:
-            return st[0], []
-        raw = self.episodes[:k].cpu()
-        rets = raw[:, 2].contiguous().view(torch.float32)
-        eps = sorted((int(raw[i, 1]), int(raw[i, 0]), float(rets[i]), int(raw[i, 3])) for i in range(k))
-        return st[0], [(e, t, r, l) for (t, e, r, l) in eps]
-
-    def _upper(self):
-        return min(self.global_step, self.slots) * self.N   # iqn.py:225
-
-    def sample(self, indices=None):
-        """batch_inds = np.random.randint(upper, size=batch_size) (iqn.py:226) under libmirl's keyed stream-4 contract; `indices` keeps the caller's batch."""
-        if indices is not None:
-            idx = torch.as_tensor(indices, dtype=torch.int64).reshape(-1).to(self.device)
-            if idx.numel() != self.batch_size:
-                raise K.MiError("sample: %d indices given, batch_size is %d" % (idx.numel(), self.batch_size))
-            self.batch_inds.copy_(idx)
-            return
-        from . import _native as N
-        if self._upper() == 0:
-            raise K.MiError("sample: the replay ring is empty (global_step == 0); act() before training")
-        N.check(N.lib().mi_dqn_sample(self.env._seed, self.update_index, self._upper(), self.batch_size, N.ptr(self.batch_inds), self._s()), "mi_dqn_sample")
-
     def force_taus(self, taus=None, next_taus=None, tau_dashes=None):
         """Teacher forcing: [B, 64] / [B, 32] / [B, 64] tau draws used by target() / grad() / train_step() until cleared with force_taus()."""
         shapes = ((self.batch_size, K.N_TAU), (self.batch_size, K.N_QUANT), (self.batch_size, K.N_TAU_PRIME))
@@ -116,7 +55,6 @@ class IQNEngine:
         self._forced = tuple(out)
 
     def _batch(self, upper):
-        # mid_event: a torch.cuda.Event's handle to be recorded between the two launches (tools/bench_iqn.py); None otherwise
         f = self._forced
         return K.IQNBatch(K.ptr(self.q.flat), K.ptr(self.target_network.flat), K.ptr(self.batch_inds), K.ptr(f[0]), K.ptr(f[1]), K.ptr(f[2]), K.ptr(self.taus),
                           K.ptr(self.current_action_quantiles), K.ptr(self.target_action_quantiles), K.ptr(self.next_actions), K.ptr(self.grads), K.ptr(self.loss),
@@ -126,35 +64,3 @@ class IQNEngine:
         """next_actions / target_action_quantiles of batch_inds from the target networks (iqn.py:252-278)."""
         b = self._batch(0)
         K.check(K.lib().mi_iqn_target(C.byref(self._ring), C.byref(b), self._s()), "mi_iqn_target")
-
-    def grad(self):
-        """loss + gradient of batch_inds (iqn.py:228-292) -> self.grads, self.loss (and taus, current / target_action_quantiles, next_actions)."""
-        b = self._batch(0)
-        K.check(K.lib().mi_iqn_grad(C.byref(self._ring), C.byref(b), self._s()), "mi_iqn_grad")
-
-    def train_step(self, indices=None):
-        """One optimisation step (iqn.py:225-293).  With deep_rl_amd.Adam: ONE call, two launches — the gradient launch draws the batch and the taus itself and the
-        launch that sums the slabs applies Adam (mi_iqn_update, bit-identical to sample() + grad() + optimizer.step())."""
-        o = self.optimizer
-        if type(o) is Adam and o.flat.data_ptr() == self.q.flat.data_ptr():
-            upper = 0
-            if indices is None:
-                upper = self._upper()
-                if upper == 0:
-                    raise K.MiError("train_step: the replay ring is empty (global_step == 0); act() before training")
-            else:
-                self.sample(indices)
-            g = o.param_groups[0]
-            b = self._batch(upper)
-            a = K.IQNAdam(K.ptr(o.exp_avg), K.ptr(o.exp_avg_sq), o.step_count + 1, float(g["lr"]), g["betas"][0], g["betas"][1], g["eps"])
-            K.check(K.lib().mi_iqn_update(C.byref(self._ring), C.byref(b), C.byref(a), self._s()), "mi_iqn_update")
-            o.step_count += 1   # committed only once the call has accepted the step
-        else:
-            self.sample(indices)
-            self.grad()
-            o.step(self.grads)
-        self.update_index += 1
-
-    def sync_target(self):
-        """target_*.load_state_dict(online_*.state_dict()) for the three modules (iqn.py:296-299)."""
-        self.target_network.flat.copy_(self.q.flat)

@@ -12,12 +12,12 @@ import pytest
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 CSRC = os.path.join(ROOT, "deep_rl_amd", "csrc")
-IQN_ALLSRC = ["mi_iqn.hip", "mi_common.h", "../../include/mi_iqn.h", "../../include/mi_rl.h"]
+IQN_ALLSRC = ["mi_iqn.hip", "mi_common.h", "mi_ring.h", "../../include/mi_iqn.h", "../../include/mi_rl.h"]
 # the three existing lists, as the parent commit's Makefile states them
 OTHER_ALLSRC = {
     "ALLSRC": "$(SRCS) mi_common.h mi_grad_kernel.inc mi_sac_rowgroup.inc ../../include/mi_rl.h",
     "PG_ALLSRC": "mi_reinforce.hip mi_common.h ../../include/mi_reinforce.h ../../include/mi_rl.h",
-    "C51_ALLSRC": "mi_c51.hip mi_common.h ../../include/mi_c51.h ../../include/mi_rl.h",
+    "C51_ALLSRC": "mi_c51.hip mi_common.h mi_ring.h ../../include/mi_c51.h ../../include/mi_rl.h",
 }
 
 
@@ -191,7 +191,7 @@ def test_engine_surface_is_callable_where_it_must_be():
     methods = ("reset", "act", "drain_episodes", "sample", "target", "grad", "train_step", "sync_target")
     for name in methods:
         assert inspect.isfunction(getattr(IQNEngine, name)), name
-    src = inspect.getsource(IQNEngine.__init__)
+    src = "".join(inspect.getsource(c.__init__) for c in IQNEngine.__mro__ if "__init__" in vars(c) and c is not object)   # the base class allocates the ring
     for name in methods:
         assert "self.%s =" % name not in src and "self.%s," % name not in src, name
     for name in ("observations", "actions", "rewards", "terminated", "batch_inds", "grads", "loss", "taus", "current_action_quantiles", "target_action_quantiles",
