@@ -13,6 +13,7 @@ from . import _native as N
 from .c51_engine import C51Engine
 from .iqn_engine import IQNEngine
 from .qrdqn_engine import QRDQNEngine
+from .ddqn_engine import DoubleDQNEngine
 from .dqn_engine import DQNEngine, DuelingDQNEngine, PERDQNEngine
 from .engine import PPOEngine
 from .reinforce_engine import ReinforceEngine
@@ -46,7 +47,7 @@ def _opt_restore(o, z, prefix):
 
 def _target_net(engine):
     """the target network of an off-policy engine (C51Engine's `target` is its method for the projected targets)"""
-    return engine.target_network if isinstance(engine, (C51Engine, IQNEngine, QRDQNEngine)) else engine.target
+    return engine.target_network if isinstance(engine, (C51Engine, IQNEngine, QRDQNEngine, DoubleDQNEngine)) else engine.target
 
 
 def state_dict(engine, include_replay=True):
@@ -56,7 +57,7 @@ def state_dict(engine, include_replay=True):
           "env_id_base": np.int64(env.env_id_base), "env_blob": _env_blob(env), "observation": engine.observation}
     if isinstance(engine, (PPOEngine, ReinforceEngine)):   # REINFORCE keeps nothing across updates but the env counters, the parameters and Adam's state
         st.update(params=engine.agent.flat, update_index=np.int64(engine.update_index), **_opt_state(engine.optimizer, "opt_"))
-    elif isinstance(engine, (DQNEngine, C51Engine, IQNEngine, QRDQNEngine)):   # C51: the same ring, two networks, one Adam
+    elif isinstance(engine, (DQNEngine, C51Engine, IQNEngine, QRDQNEngine, DoubleDQNEngine)):   # C51: the same ring, two networks, one Adam
         st.update(params=engine.q.flat, target=_target_net(engine).flat, global_step=np.int64(engine.global_step), update_index=np.int64(engine.update_index),
                   **_opt_state(engine.optimizer, "opt_"))
         if isinstance(engine, PERDQNEngine):
@@ -114,7 +115,7 @@ def load(path, engine):
     _env_restore(env, z["env_blob"])
     if isinstance(engine, (PPOEngine, ReinforceEngine)):
         _check_shape(z, "params", engine.agent.flat.shape)
-    elif isinstance(engine, (DQNEngine, C51Engine, IQNEngine, QRDQNEngine)):
+    elif isinstance(engine, (DQNEngine, C51Engine, IQNEngine, QRDQNEngine, DoubleDQNEngine)):
         _check_shape(z, "params", engine.q.flat.shape); _check_shape(z, "target", _target_net(engine).flat.shape)
     else:
         _check_shape(z, "actor", engine.actor.flat.shape); _check_shape(z, "q", engine.q_flat.shape); _check_shape(z, "q_target", engine.qt_flat.shape)
@@ -124,7 +125,7 @@ def load(path, engine):
     engine.observation = t("observation")
     if isinstance(engine, (PPOEngine, ReinforceEngine)):
         engine.agent.flat.copy_(t("params")); engine.update_index = int(z["update_index"]); _opt_restore(engine.optimizer, z, "opt_")
-    elif isinstance(engine, (DQNEngine, C51Engine, IQNEngine, QRDQNEngine)):
+    elif isinstance(engine, (DQNEngine, C51Engine, IQNEngine, QRDQNEngine, DoubleDQNEngine)):
         engine.q.flat.copy_(t("params")); _target_net(engine).flat.copy_(t("target"))
         if isinstance(engine, DuelingDQNEngine):
             engine.q.repack(); engine.target.repack()
