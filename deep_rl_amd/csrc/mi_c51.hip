@@ -7,10 +7,12 @@
 //   c51_grad_kernel     a workgroup walks its batch rows twice: with the TARGET network it writes next_actions / target_probs (softmax, greedy action, categorical
 //                       projection per target atom), then with the ONLINE network forward + backward of the same rows into register accumulators — one slab per workgroup.
 //   c51_reduce_kernel   fixed-order slab sum (+ Adam).
-// All arithmetic on the VALU in fp32 with the summation orders of the header; no floating-point atomics.
+// The torso (layout, loader, ts_row, ts_backward, ts_store) is mi_torso.h's, shared with mi_qr.hip and mi_ddqn.hip; the host side of acting and of the gradient entry
+// points is mi_ring.h's.  All arithmetic on the VALU in fp32 with the summation orders of the header; no floating-point atomics.
 // Uses mi_common.h read-only for the device helpers; none of its host-side macros (they call into libmirl.so).
 #include "mi_common.h"
 #include "mi_ring.h"
+#include "mi_torso.h"
 
 #include "../../include/mi_c51.h"
 
@@ -18,16 +20,12 @@
 #define C5_H2 MI_C51_H2
 #define C5_NA MI_C51_N_ATOMS
 #define C5_NL (2 * MI_C51_N_ATOMS)
-#define C5_W1 MI_C51_W1
-#define C5_B1 MI_C51_B1
-#define C5_W2 MI_C51_W2
-#define C5_B2 MI_C51_B2
 #define C5_W3 MI_C51_W3
 #define C5_B3 MI_C51_B3
 #define C5_NP MI_C51_NPARAMS
 #define C5_STRIDE MI_C51_SLAB_STRIDE
-#define C5_W2C 40              // columns of W2 per thread (three threads per row)
 static_assert(MI_C51_OK == RG_OK && MI_C51_EINVAL == RG_EINVAL && MI_C51_EHIP == RG_EHIP && MI_C51_MAX_STEPS_PER_CALL == RG_MAX_STEPS, "mi_ring.h returns these");
+static_assert(MI_C51_W1 == TS_W1 && MI_C51_B1 == TS_B1 && MI_C51_W2 == TS_W2 && MI_C51_B2 == TS_B2 && MI_C51_H1 == TS_H1 && MI_C51_H2 == TS_H2, "mi_torso.h holds this torso");
 
 #ifndef MI_C51_SOURCE_ID
 #define MI_C51_SOURCE_ID "unknown"
@@ -44,8 +42,7 @@ extern "C" size_t mi_c51_workspace_bytes(int batch) {
 // ---- the network as one workgroup holds it ------------------------------------------------------------
 struct c5_weights {
     float w3[C5_H2]; float b3;          // thread r < 202: row r of W3
-    float w2[C5_W2C]; float b2;         // thread c * 84 + o < 252: W2[o][40 c .. 40 c + 39]; b2 is the chain's start (the bias for c = 0, else 0)
-    float w1[4]; float b1;              // thread u < 120
+    ts_torso ts;
 };
 struct c5_smem {
     float h1[C5_H1];
@@ -69,20 +66,7 @@ __device__ __forceinline__ void c5_load_weights(c5_weights& w, const float* __re
         for (int k = 0; k < C5_H2 / 4; ++k) { const float4 v = src[k]; w.w3[4 * k] = v.x; w.w3[4 * k + 1] = v.y; w.w3[4 * k + 2] = v.z; w.w3[4 * k + 3] = v.w; }
         w.b3 = P[C5_B3 + r];
     }
-    {
-        const int tt = t < 3 * C5_H2 ? t : 3 * C5_H2 - 1;
-        const int c = tt / C5_H2, o = tt - c * C5_H2;
-        const float4* src = reinterpret_cast<const float4*>(P + C5_W2 + (size_t)o * C5_H1 + C5_W2C * c);   // 600, 120 and 40 are multiples of 4
-#pragma unroll
-        for (int k = 0; k < C5_W2C / 4; ++k) { const float4 v = src[k]; w.w2[4 * k] = v.x; w.w2[4 * k + 1] = v.y; w.w2[4 * k + 2] = v.z; w.w2[4 * k + 3] = v.w; }
-        w.b2 = c == 0 ? P[C5_B2 + o] : 0.0f;
-    }
-    {
-        const int u = t < C5_H1 ? t : C5_H1 - 1;
-        const float4 v = reinterpret_cast<const float4*>(P + C5_W1)[u];
-        w.w1[0] = v.x; w.w1[1] = v.y; w.w1[2] = v.z; w.w1[3] = v.w;
-        w.b1 = P[C5_B1 + u];
-    }
+    ts_load(w.ts, P, t);
 }
 
 // the balanced pairwise sum over the 64 lanes in natural order (mi_c51.h: TREE2's second half), result in every lane, VALU only
@@ -102,23 +86,7 @@ __device__ __forceinline__ float c5_atom(int j) { return MI_C51_V_MIN + 2.0f * (
 
 // layers 1 - 3 of one row: sm.h1, sm.h2, sm.logit are valid for every thread when it returns
 __device__ __forceinline__ void c5_forward_row(const c5_weights& w, const float4 x, c5_smem& sm, int t) {
-    if (t < C5_H1) {
-        float z = w.b1;
-        z = __builtin_fmaf(w.w1[0], x.x, z); z = __builtin_fmaf(w.w1[1], x.y, z);
-        z = __builtin_fmaf(w.w1[2], x.z, z); z = __builtin_fmaf(w.w1[3], x.w, z);
-        sm.h1[t] = fmaxf(z, 0.0f);
-    }
-    __syncthreads();
-    if (t < 3 * C5_H2) {
-        const int c = t / C5_H2, o = t - c * C5_H2;
-        float acc = w.b2;
-#pragma unroll
-        for (int k = 0; k < C5_W2C; ++k) acc = __builtin_fmaf(w.w2[k], sm.h1[C5_W2C * c + k], acc);
-        sm.p2[c][o] = acc;
-    }
-    __syncthreads();
-    if (t < C5_H2) sm.h2[t] = fmaxf((sm.p2[0][t] + sm.p2[1][t]) + sm.p2[2][t], 0.0f);
-    __syncthreads();
+    ts_row(w.ts, x, sm, t);
     if (t < C5_NL) {
         float acc = w.b3;
 #pragma unroll
@@ -279,12 +247,11 @@ __global__ void __launch_bounds__(256) c51_grad_kernel(mi_c51_ring_t ring, mi_c5
     __syncthreads();
     // ---- pass 2, online network: forward + backward into register accumulators ----
     c5_load_weights(w, bt.params, t);
-    float g3[C5_H2], g2[C5_W2C], g1[4] = {0.0f, 0.0f, 0.0f, 0.0f};
-    float gb3 = 0.0f, gb2 = 0.0f, gb1 = 0.0f, loss = 0.0f;
+    float g3[C5_H2], gb3 = 0.0f, loss = 0.0f;
+    ts_grads g;
 #pragma unroll
     for (int k = 0; k < C5_H2; ++k) g3[k] = 0.0f;
-#pragma unroll
-    for (int k = 0; k < C5_W2C; ++k) g2[k] = 0.0f;
+    ts_zero(g);
     const float invB = 1.0f / (float)bt.batch;
     const float* __restrict__ P = bt.params;
     for (int b = blockIdx.x; b < bt.batch; b += gridDim.x) {
@@ -333,28 +300,7 @@ __global__ void __launch_bounds__(256) c51_grad_kernel(mi_c51_ring_t ring, mi_c5
         __syncthreads();
         if (t < C5_H2) sm.dz2[t] = sm.h2[t] > 0.0f ? (sm.p2[0][t] + sm.p2[1][t]) + sm.p2[2][t] : 0.0f;
         __syncthreads();
-        if (t < 3 * C5_H2) {
-            const int c = t / C5_H2, o = t - c * C5_H2;
-            const float d = sm.dz2[o];
-            if (c == 0) gb2 += d;
-#pragma unroll
-            for (int k = 0; k < C5_W2C; ++k) g2[k] = __builtin_fmaf(d, sm.h1[C5_W2C * c + k], g2[k]);
-        }
-        if (t < 2 * C5_H1) {
-            const int c = t / C5_H1, k = t - c * C5_H1;
-            const float* const col = P + C5_W2 + k;
-            float acc = 0.0f;
-            for (int o = 42 * c; o < 42 * c + 42; ++o) acc = __builtin_fmaf(sm.dz2[o], col[(size_t)o * C5_H1], acc);
-            sm.ph[c][k] = acc;
-        }
-        __syncthreads();
-        if (t < C5_H1) {
-            const float d = sm.h1[t] > 0.0f ? sm.ph[0][t] + sm.ph[1][t] : 0.0f;
-            gb1 += d;
-            g1[0] = __builtin_fmaf(d, x.x, g1[0]); g1[1] = __builtin_fmaf(d, x.y, g1[1]);
-            g1[2] = __builtin_fmaf(d, x.z, g1[2]); g1[3] = __builtin_fmaf(d, x.w, g1[3]);
-        }
-        __syncthreads();
+        ts_backward(g, sm.h1, sm.dz2, sm.ph, x, P, t);
     }
     // ---- the workgroup's slab ----
     float* const slab = slabs + (size_t)blockIdx.x * C5_STRIDE;
@@ -364,17 +310,7 @@ __global__ void __launch_bounds__(256) c51_grad_kernel(mi_c51_ring_t ring, mi_c5
         for (int k = 0; k < C5_H2 / 4; ++k) dst[k] = make_float4(g3[4 * k], g3[4 * k + 1], g3[4 * k + 2], g3[4 * k + 3]);
         slab[C5_B3 + t] = gb3;
     }
-    if (t < 3 * C5_H2) {
-        const int c = t / C5_H2, o = t - c * C5_H2;
-        float4* const dst = reinterpret_cast<float4*>(slab + C5_W2 + (size_t)o * C5_H1 + C5_W2C * c);
-#pragma unroll
-        for (int k = 0; k < C5_W2C / 4; ++k) dst[k] = make_float4(g2[4 * k], g2[4 * k + 1], g2[4 * k + 2], g2[4 * k + 3]);
-        if (c == 0) slab[C5_B2 + o] = gb2;
-    }
-    if (t < C5_H1) {
-        reinterpret_cast<float4*>(slab + C5_W1)[t] = make_float4(g1[0], g1[1], g1[2], g1[3]);
-        slab[C5_B1 + t] = gb1;
-    }
+    ts_store(g, slab, t);
     if (t == 0) { slab[C5_NP] = loss; slab[C5_NP + 1] = 0.0f; }
 }
 
@@ -398,19 +334,13 @@ extern "C" int mi_c51_act_steps(void* handle, const float* params, int n_steps, 
                                 mi_episode_t* episodes, int32_t* episode_stats, int max_ep, void* stream) {
     const mi_env* e = (const mi_env*)handle;
     RG_CHECK_ARG(e != nullptr && params && obs_cur, "NULL pointer");
-    RG_CHECK_ARG(rg_aligned(params) && rg_aligned(obs_cur), "params and obs_cur must be 16-byte aligned");
-    const int rc = rg_check_ring(ring);
-    if (rc != MI_C51_OK) return rc;
-    RG_CHECK_ARG(e->kind == MI_ENV_CARTPOLE_V1 && e->n > 0, "env is not a CartPole-v1 handle");
-    RG_CHECK_ARG(e->n == ring->n_envs, "the ring's n_envs is not the handle's");
-    RG_CHECK_ARG(n_steps > 0 && n_steps <= MI_C51_MAX_STEPS_PER_CALL, "n_steps must be in [1, 64]");
     RG_CHECK_ARG(global_step >= 0 && total_timesteps > 0 && exploration_fraction > 0.0, "global_step < 0, total_timesteps <= 0 or exploration_fraction <= 0");
-    RG_CHECK_ARG(max_ep >= 0 && (max_ep == 0 || (episodes && episode_stats)), "episodes / episode_stats buffer missing");
     hipStream_t s = (hipStream_t)stream;
     rg_eps_tab tab;
     rg_eps_fill(tab, global_step, (end_e - start_e) / (exploration_fraction * (double)total_timesteps), start_e, end_e);
-    if (episode_stats) RG_HIP(hipMemsetAsync(episode_stats, 0, 4 * sizeof(int32_t), s));
-    const int grid = e->n < 1024 ? e->n : 1024;
+    int grid;
+    const int rc = rg_act_prelude(e, ring, params, obs_cur, n_steps, max_ep, episodes, episode_stats, s, grid);
+    if (rc != MI_C51_OK) return rc;
     if (forced_actions || forced_resets)
         c51_act_kernel<true><<<grid, 256, 0, s>>>(*e, params, n_steps, (long long)global_step, *ring, tab, obs_cur, forced_actions, forced_resets, episodes, episode_stats, max_ep);
     else
@@ -430,36 +360,14 @@ extern "C" int mi_c51_target(const float* target_params, const mi_c51_ring_t* ri
     return MI_C51_OK;
 }
 
-static int c5_check_batch(const mi_c51_ring_t* ring, const mi_c51_batch_t* b) {
-    const int rc = rg_check_ring(ring);
-    if (rc != MI_C51_OK) return rc;
-    RG_CHECK_ARG(b != nullptr, "batch is NULL");
-    RG_CHECK_ARG(b->batch > 0, "batch <= 0");
-    RG_CHECK_ARG(b->params && b->target_params && b->idx && b->target_probs && b->next_actions && b->grads && b->loss && b->workspace, "a batch buffer is NULL");
-    RG_CHECK_ARG(rg_aligned(b->params) && rg_aligned(b->target_params) && rg_aligned(b->workspace), "params, target_params and workspace must be 16-byte aligned");
-    RG_CHECK_ARG(b->sample_upper >= 0 && b->sample_upper <= ring->slots * (int64_t)ring->n_envs, "sample_upper outside [0, slots * n_envs]");
-    return MI_C51_OK;
+// mi_c51_grad (update false: opt is not looked at) and mi_c51_update
+static int c5_grad(const mi_c51_ring_t* ring, const mi_c51_batch_t* b, const mi_c51_adam_t* opt, bool update, hipStream_t s) {
+    int rc = rg_check_batch(ring, b, INT_MAX, "batch <= 0", [](const mi_c51_batch_t& bt) { return bt.target_probs != nullptr; });
+    if (rc == RG_OK && update) rc = rg_check_opt(opt);
+    if (rc != RG_OK) return rc;
+    return rg_launch_grad<C5_NP>(c51_grad_kernel, c51_reduce_kernel, ring, b, c5_slabs(b->batch), 1.0f / (float)b->batch, update ? opt : nullptr, s);
 }
-static int c5_launch_grad(const mi_c51_ring_t* ring, const mi_c51_batch_t* b, float* p, float* m, float* v, const rg_adam_consts& k, int adam, hipStream_t s) {
-    const int slabs = c5_slabs(b->batch);
-    c51_grad_kernel<<<slabs, 256, 0, s>>>(*ring, *b, (float*)b->workspace);
-    RG_HIP(hipGetLastError());
-    if (b->mid_event) RG_HIP(hipEventRecord((hipEvent_t)b->mid_event, s));
-    c51_reduce_kernel<<<(C5_NP + 1 + 31) / 32, 32 * RG_RED_GROUPS, 0, s>>>((const float*)b->workspace, slabs, 1.0f / (float)b->batch, b->grads, b->loss, p, m, v, k, adam);
-    RG_HIP(hipGetLastError());
-    return MI_C51_OK;
-}
-
-extern "C" int mi_c51_grad(const mi_c51_ring_t* ring, const mi_c51_batch_t* b, void* stream) {
-    const int rc = c5_check_batch(ring, b);
-    if (rc != MI_C51_OK) return rc;
-    return c5_launch_grad(ring, b, nullptr, nullptr, nullptr, rg_adam_consts{}, 0, (hipStream_t)stream);
-}
-
+extern "C" int mi_c51_grad(const mi_c51_ring_t* ring, const mi_c51_batch_t* b, void* stream) { return c5_grad(ring, b, nullptr, false, (hipStream_t)stream); }
 extern "C" int mi_c51_update(const mi_c51_ring_t* ring, const mi_c51_batch_t* b, const mi_c51_adam_t* opt, void* stream) {
-    const int rc = c5_check_batch(ring, b);
-    if (rc != MI_C51_OK) return rc;
-    RG_CHECK_ARG(opt != nullptr, "opt is NULL");
-    RG_CHECK_ARG(opt->exp_avg && opt->exp_avg_sq && opt->step >= 1, "an optimizer buffer is NULL or step < 1");
-    return c5_launch_grad(ring, b, (float*)b->params, opt->exp_avg, opt->exp_avg_sq, rg_adam_host(opt->step, opt->lr, opt->beta1, opt->beta2, opt->eps), 1, (hipStream_t)stream);
+    return c5_grad(ring, b, opt, true, (hipStream_t)stream);
 }

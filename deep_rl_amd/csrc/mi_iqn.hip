@@ -525,20 +525,13 @@ extern "C" int mi_iqn_forward(const float* params, const float* obs, const float
 extern "C" int mi_iqn_act_steps(void* handle, const mi_iqn_ring_t* ring, const mi_iqn_act_t* a, void* stream) {
     const mi_env* e = (const mi_env*)handle;
     RG_CHECK_ARG(e != nullptr && a != nullptr, "NULL pointer");
-    RG_CHECK_ARG(a->params && a->obs_cur, "params or obs_cur is NULL");
-    RG_CHECK_ARG(rg_aligned(a->params) && rg_aligned(a->obs_cur), "params and obs_cur must be 16-byte aligned");
-    const int rc = rg_check_ring(ring);
-    if (rc != MI_IQN_OK) return rc;
-    RG_CHECK_ARG(e->kind == MI_ENV_CARTPOLE_V1 && e->n > 0, "env is not a CartPole-v1 handle");
-    RG_CHECK_ARG(e->n == ring->n_envs, "the ring's n_envs is not the handle's");
-    RG_CHECK_ARG(a->n_steps > 0 && a->n_steps <= MI_IQN_MAX_STEPS_PER_CALL, "n_steps must be in [1, 64]");
     RG_CHECK_ARG(a->global_step >= 0 && a->learning_starts >= 0, "global_step < 0 or learning_starts < 0");
-    RG_CHECK_ARG(a->max_ep >= 0 && (a->max_ep == 0 || (a->episodes && a->episode_stats)), "episodes / episode_stats buffer missing");
     hipStream_t s = (hipStream_t)stream;
     rg_eps_tab tab;
     rg_eps_fill(tab, a->global_step, a->slope, 1.0, a->final_epsilon);   // epsilon = max(1 + slope * step, final_epsilon)
-    if (a->episode_stats) RG_HIP(hipMemsetAsync(a->episode_stats, 0, 4 * sizeof(int32_t), s));
-    const int grid = e->n < 1024 ? e->n : 1024;
+    int grid;
+    const int rc = rg_act_prelude(e, ring, a->params, a->obs_cur, a->n_steps, a->max_ep, a->episodes, a->episode_stats, s, grid);
+    if (rc != MI_IQN_OK) return rc;
     if (a->forced_actions || a->forced_resets || a->forced_taus)
         iqn_act_kernel<true><<<grid, 256, 0, s>>>(*e, *ring, *a, tab);
     else
@@ -567,38 +560,14 @@ extern "C" int mi_iqn_quantile_huber(const float* current, const float* target, 
     return MI_IQN_OK;
 }
 
-static int iq_check_batch(const mi_iqn_ring_t* ring, const mi_iqn_batch_t* b) {
-    const int rc = rg_check_ring(ring);
-    if (rc != MI_IQN_OK) return rc;
-    RG_CHECK_ARG(b != nullptr, "batch is NULL");
-    RG_CHECK_ARG(b->batch > 0 && b->batch <= (1 << 24), "batch must be in [1, 2^24]");
-    RG_CHECK_ARG(b->params && b->target_params && b->idx && b->taus && b->current && b->target && b->next_actions && b->grads && b->loss && b->workspace,
-                 "a batch buffer is NULL");
-    RG_CHECK_ARG(rg_aligned(b->params) && rg_aligned(b->target_params) && rg_aligned(b->workspace), "params, target_params and workspace must be 16-byte aligned");
-    RG_CHECK_ARG(b->sample_upper >= 0 && b->sample_upper <= ring->slots * (int64_t)ring->n_envs, "sample_upper outside [0, slots * n_envs]");
-    return MI_IQN_OK;
+// mi_iqn_grad (update false: opt is not looked at) and mi_iqn_update
+static int iq_grad(const mi_iqn_ring_t* ring, const mi_iqn_batch_t* b, const mi_iqn_adam_t* opt, bool update, hipStream_t s) {
+    int rc = rg_check_batch(ring, b, 1 << 24, "batch must be in [1, 2^24]", [](const mi_iqn_batch_t& bt) { return bt.taus && bt.current && bt.target; });
+    if (rc == RG_OK && update) rc = rg_check_opt(opt);
+    if (rc != RG_OK) return rc;
+    return rg_launch_grad<IQ_NP>(iqn_grad_kernel, iqn_reduce_kernel, ring, b, iq_slabs(b->batch), 1.0f / (float)(b->batch * 64), update ? opt : nullptr, s);
 }
-static int iq_launch_grad(const mi_iqn_ring_t* ring, const mi_iqn_batch_t* b, float* p, float* m, float* v, const rg_adam_consts& k, int adam, hipStream_t s) {
-    const int slabs = iq_slabs(b->batch);
-    iqn_grad_kernel<<<slabs, 256, 0, s>>>(*ring, *b, (float*)b->workspace);
-    RG_HIP(hipGetLastError());
-    if (b->mid_event) RG_HIP(hipEventRecord((hipEvent_t)b->mid_event, s));
-    iqn_reduce_kernel<<<(IQ_NP + 1 + 31) / 32, 32 * RG_RED_GROUPS, 0, s>>>((const float*)b->workspace, slabs, 1.0f / (float)(b->batch * 64), b->grads, b->loss, p, m, v, k,
-                                                                           adam);
-    RG_HIP(hipGetLastError());
-    return MI_IQN_OK;
-}
-
-extern "C" int mi_iqn_grad(const mi_iqn_ring_t* ring, const mi_iqn_batch_t* b, void* stream) {
-    const int rc = iq_check_batch(ring, b);
-    if (rc != MI_IQN_OK) return rc;
-    return iq_launch_grad(ring, b, nullptr, nullptr, nullptr, rg_adam_consts{}, 0, (hipStream_t)stream);
-}
-
+extern "C" int mi_iqn_grad(const mi_iqn_ring_t* ring, const mi_iqn_batch_t* b, void* stream) { return iq_grad(ring, b, nullptr, false, (hipStream_t)stream); }
 extern "C" int mi_iqn_update(const mi_iqn_ring_t* ring, const mi_iqn_batch_t* b, const mi_iqn_adam_t* opt, void* stream) {
-    const int rc = iq_check_batch(ring, b);
-    if (rc != MI_IQN_OK) return rc;
-    RG_CHECK_ARG(opt != nullptr, "opt is NULL");
-    RG_CHECK_ARG(opt->exp_avg && opt->exp_avg_sq && opt->step >= 1, "an optimizer buffer is NULL or step < 1");
-    return iq_launch_grad(ring, b, (float*)b->params, opt->exp_avg, opt->exp_avg_sq, rg_adam_host(opt->step, opt->lr, opt->beta1, opt->beta2, opt->eps), 1, (hipStream_t)stream);
+    return iq_grad(ring, b, opt, true, (hipStream_t)stream);
 }

@@ -1,10 +1,11 @@
-// mi_ring.h — what the ring-replay libraries (libmirl_c51.so, libmirl_iqn.so, libmirl_qr.so) have in common: the error plumbing, the argument checks of the replay
-// ring, the epsilon table, the acting loop, the minibatch row index and the fixed-order slab sum (+ Adam).  Each library is ONE translation unit that includes this
-// header once, so every `static` / `static thread_local` below is that library's own copy; nothing here is exported.
+// mi_ring.h — what the ring-replay libraries (libmirl_c51.so, libmirl_iqn.so, libmirl_qr.so, libmirl_ddqn.so) have in common: the error plumbing, the argument checks
+// of the replay ring, of an acting call, of a batch and of the optimizer state, the epsilon table, the acting loop, the minibatch row index, the gradient launch and
+// the fixed-order slab sum (+ Adam).  Each library is ONE translation unit that includes this header once, so every `static` / `static thread_local` below is that
+// library's own copy; nothing here is exported.
 //
-// A library supplies its network (layout, loaders, forward / target / loss / gradient kernels), its argument checks, its `__global__` entry points and a POLICY
-// struct for rg_act_loop; its MI_X_OK / MI_X_EINVAL / MI_X_EHIP must be 0 / -1 / -2 and its MI_X_MAX_STEPS_PER_CALL must be RG_MAX_STEPS (static_assert them).
-// Uses mi_common.h read-only for the device helpers; none of its host-side macros (they call into libmirl.so).
+// A library supplies its network (layout, loaders, forward / target / loss / gradient kernels), the argument checks that are its own, its `__global__` entry points
+// and a POLICY struct for rg_act_loop; its MI_X_OK / MI_X_EINVAL / MI_X_EHIP must be 0 / -1 / -2 and its MI_X_MAX_STEPS_PER_CALL must be RG_MAX_STEPS (static_assert
+// them).  Uses mi_common.h read-only for the device helpers; none of its host-side macros (they call into libmirl.so).
 #pragma once
 #include "mi_common.h"
 
@@ -43,7 +44,7 @@ static void rg_set_error(const char* fmt, ...) {
 
 static bool rg_aligned(const void* p) { return ((uintptr_t)p & 15u) == 0; }   // parameters, observations and slabs are read and written as float4
 static int rg_slabs(int batch, int max_slabs) { return batch < max_slabs ? batch : max_slabs; }
-// RING: mi_c51_ring_t / mi_iqn_ring_t / mi_qr_ring_t (the same members; every use below is by name, so nothing is cast between them)
+// RING: mi_c51_ring_t / mi_iqn_ring_t / mi_qr_ring_t / mi_ddqn_ring_t, and BATCH / ADAM below likewise (the same members; every use below is by name, so nothing is cast between them)
 template <class RING>
 static int rg_check_ring(const RING* r) {
     RG_CHECK_ARG(r != nullptr, "ring is NULL");
@@ -154,6 +155,25 @@ __device__ __forceinline__ void rg_act_loop(const mi_env& e, const RING& ring, c
     if (t == 0 && a_.episode_stats && st_cnt > 0) { atomicAdd(a_.episode_stats, st_cnt); atomicAdd(a_.episode_stats + 1, st_len); atomicMax(a_.episode_stats + 2, st_max); }
 }
 
+// The host side of mi_x_act_steps behind the library's own checks (its act struct, its schedule) and its epsilon table: the checks the four share, the statistics
+// memset and the grid.  The library then picks FORCED and launches its kernel.
+template <class RING>
+static int rg_act_prelude(const mi_env* e, const RING* ring, const float* params, const float* obs_cur, int n_steps, int max_ep, const mi_episode_t* episodes,
+                          int32_t* episode_stats, hipStream_t s, int& grid) {
+    RG_CHECK_ARG(e != nullptr, "NULL pointer");
+    RG_CHECK_ARG(params && obs_cur, "params or obs_cur is NULL");
+    RG_CHECK_ARG(rg_aligned(params) && rg_aligned(obs_cur), "params and obs_cur must be 16-byte aligned");
+    const int rc = rg_check_ring(ring);
+    if (rc != RG_OK) return rc;
+    RG_CHECK_ARG(e->kind == MI_ENV_CARTPOLE_V1 && e->n > 0, "env is not a CartPole-v1 handle");
+    RG_CHECK_ARG(e->n == ring->n_envs, "the ring's n_envs is not the handle's");
+    RG_CHECK_ARG(n_steps > 0 && n_steps <= RG_MAX_STEPS, "n_steps must be in [1, 64]");
+    RG_CHECK_ARG(max_ep >= 0 && (max_ep == 0 || (episodes && episode_stats)), "episodes / episode_stats buffer missing");
+    if (episode_stats) RG_HIP(hipMemsetAsync(episode_stats, 0, 4 * sizeof(int32_t), s));
+    grid = e->n < 1024 ? e->n : 1024;
+    return RG_OK;
+}
+
 // ---- minibatch rows ---------------------------------------------------------------------------------
 // the flat ring index of batch row b: drawn in the launch when upper > 0 (Philox stream 4, keyed by the update index; the thread with `store` set writes it to
 // idx[b]), else read from idx[b].  A bad index reads a valid row, never past the ring.
@@ -215,4 +235,39 @@ __device__ __forceinline__ void rg_reduce(const float* __restrict__ slabs, int n
         p[i] = mi_adam_elem(p[i], sum, mi, vi, k.w1, k.b2, k.w2, k.step_size, k.rbc2, k.eps);
         m[i] = mi; v[i] = vi;
     }
+}
+
+// ---- the gradient entry points (mi_x_grad / mi_x_update) ----------------------------------------------
+// `own` is the library's part of "every buffer is there" (the members only its batch struct has), max_batch / batch_msg its bound on the batch
+template <class RING, class BATCH, class OWN>
+static int rg_check_batch(const RING* ring, const BATCH* b, int max_batch, const char* batch_msg, OWN own) {
+    const int rc = rg_check_ring(ring);
+    if (rc != RG_OK) return rc;
+    RG_CHECK_ARG(b != nullptr, "batch is NULL");
+    RG_CHECK_ARG(b->batch > 0 && b->batch <= max_batch, batch_msg);
+    RG_CHECK_ARG(b->params && b->target_params && b->idx && b->next_actions && b->grads && b->loss && b->workspace && own(*b), "a batch buffer is NULL");
+    RG_CHECK_ARG(rg_aligned(b->params) && rg_aligned(b->target_params) && rg_aligned(b->workspace), "params, target_params and workspace must be 16-byte aligned");
+    RG_CHECK_ARG(b->sample_upper >= 0 && b->sample_upper <= ring->slots * (int64_t)ring->n_envs, "sample_upper outside [0, slots * n_envs]");
+    return RG_OK;
+}
+template <class ADAM>
+static int rg_check_opt(const ADAM* opt) {
+    RG_CHECK_ARG(opt != nullptr, "opt is NULL");
+    RG_CHECK_ARG(opt->exp_avg && opt->exp_avg_sq && opt->step >= 1, "an optimizer buffer is NULL or step < 1");
+    return RG_OK;
+}
+// the gradient launch over `slabs` workgroups, the optional mid_event, the slab sum scaled by `inv`; with opt != NULL (checked) the sum's Adam step on b->params
+using rg_reduce_fn = void (*)(const float*, int, float, float*, float*, float*, float*, float*, rg_adam_consts, int);
+template <int NP, class RING, class BATCH, class ADAM>
+static int rg_launch_grad(void (*grad)(RING, BATCH, float*), rg_reduce_fn reduce, const RING* ring, const BATCH* b, int slabs, float inv, const ADAM* opt, hipStream_t s) {
+    grad<<<slabs, 256, 0, s>>>(*ring, *b, (float*)b->workspace);
+    RG_HIP(hipGetLastError());
+    if (b->mid_event) RG_HIP(hipEventRecord((hipEvent_t)b->mid_event, s));
+    if (opt)
+        reduce<<<(NP + 1 + 31) / 32, 32 * RG_RED_GROUPS, 0, s>>>((const float*)b->workspace, slabs, inv, b->grads, b->loss, (float*)b->params, opt->exp_avg, opt->exp_avg_sq,
+                                                                 rg_adam_host(opt->step, opt->lr, opt->beta1, opt->beta2, opt->eps), 1);
+    else
+        reduce<<<(NP + 1 + 31) / 32, 32 * RG_RED_GROUPS, 0, s>>>((const float*)b->workspace, slabs, inv, b->grads, b->loss, nullptr, nullptr, nullptr, rg_adam_consts{}, 0);
+    RG_HIP(hipGetLastError());
+    return RG_OK;
 }

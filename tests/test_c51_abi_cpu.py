@@ -12,7 +12,7 @@ import pytest
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 CSRC = os.path.join(ROOT, "deep_rl_amd", "csrc")
-C51_ALLSRC = ["mi_c51.hip", "mi_common.h", "mi_ring.h", "../../include/mi_c51.h", "../../include/mi_rl.h"]
+C51_ALLSRC = ["mi_c51.hip", "mi_common.h", "mi_ring.h", "mi_torso.h", "../../include/mi_c51.h", "../../include/mi_rl.h"]
 
 
 @pytest.fixture(scope="module")

@@ -12,7 +12,7 @@ import pytest
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 CSRC = os.path.join(ROOT, "deep_rl_amd", "csrc")
-QR_ALLSRC = ["mi_qr.hip", "mi_common.h", "mi_ring.h", "../../include/mi_qr.h", "../../include/mi_rl.h"]
+QR_ALLSRC = ["mi_qr.hip", "mi_common.h", "mi_ring.h", "mi_torso.h", "../../include/mi_qr.h", "../../include/mi_rl.h"]
 
 
 @pytest.fixture(scope="module")
@@ -179,7 +179,7 @@ def test_the_other_libraries_are_still_the_profiled_ones(K):
 
     inc = "../../include/"
     assert srcid(["mi_reinforce.hip", "mi_common.h", inc + "mi_reinforce.h", inc + "mi_rl.h"]) == PG.source_id()
-    assert srcid(["mi_c51.hip", "mi_common.h", "mi_ring.h", inc + "mi_c51.h", inc + "mi_rl.h"]) == C5.source_id()
+    assert srcid(["mi_c51.hip", "mi_common.h", "mi_ring.h", "mi_torso.h", inc + "mi_c51.h", inc + "mi_rl.h"]) == C5.source_id()
     assert srcid(["mi_iqn.hip", "mi_common.h", "mi_ring.h", inc + "mi_iqn.h", inc + "mi_rl.h"]) == IQ.source_id()
     assert PG.source_id() in open(os.path.join(ROOT, "profiles", "reinforce_bench.json")).read()
     assert json.load(open(os.path.join(ROOT, "profiles", "c51_bench.json")))["c51_source_id"] == C5.source_id()
