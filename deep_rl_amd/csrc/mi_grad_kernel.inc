@@ -13,19 +13,25 @@ struct __attribute__((aligned(16))) GV(grad_weights) {
     float W3[2 * HID];
     float W1s[HID * OBS];                 // c W1[unit][k]: every wave picks its layer-1 A fragments from here after the staging barrier
     float b3s[4];
+    // Wave-private staging, ONE contiguous block per wave (13 KB): every tile-loop access of a wave is `its base + an immediate offset`.
+    // xs: the tile's observations TRANSPOSED, x[k][row]: written as 64 consecutive dwords (lane (j, g) -> g * 16 + j), read back for dW1 as four b128 per lane
+    // = x[lane & 3][0..15] (4 distinct 16-byte addresses 64 B apart, broadcast over the lanes that share k: conflict-free) instead of sixteen b32 of a [row][k] image.
+    struct {
 #if GRAD_BX
-    // wave-private transposed images for dW2 (layout: bx_store_image), read back as one b128 per lane = 8 rows of one unit.
-    // imgH (h1) is dead once the dW2 MFMAs have read it; the [row][unit] f32 staging tile of dz1 (bufB) then reuses its bytes (LDS operations of
-    // one wave execute in order).
-    union { unsigned short imgH[BX_IMG]; float bufB[TROWS * W2S]; } hb[GRAD_WAVES];
-    unsigned short imgZ[GRAD_WAVES][BX_IMG];
-    float xs[GRAD_WAVES][TROWS * 4];       // x[row][0..3]
+        // transposed images for dW2 (layout: bx_store_image), read back as one b128 per lane = 8 rows of one unit.
+        // imgH (h1) is dead once the dW2 MFMAs have read it; the [row][unit] f32 staging tile of dz1 (bufB) then reuses its bytes (LDS operations of
+        // one wave execute in order).
+        union { unsigned short imgH[BX_IMG]; float bufB[TROWS * W2S]; } hb;
+        unsigned short imgZ[BX_IMG];
 #else
-    float bufA[GRAD_WAVES][TROWS * W2S];   // wave-private [row][unit] images for the transposed re-reads; the 4 pad
-    float bufB[GRAD_WAVES][TROWS * W2S];   // columns (64..67) of a bufA row hold x[row][0..3]
-    float bufC[GRAD_WAVES][TROWS * W2S];   // bufA: h1 (+ x), bufB: dz1, bufC: dz2 — each written as soon as its tile exists, read phases later
+        float bufA[TROWS * W2S];   // [row][unit] images for the transposed re-reads (row stride W2S: the 4 pad columns are unused)
+        float bufB[TROWS * W2S];   // bufA: h1, bufB: dz1, bufC: dz2 — each written as soon as its tile exists, read phases later
+        float bufC[TROWS * W2S];
 #endif
+        float xs[4 * TROWS];
+    } __attribute__((aligned(16))) st[GRAD_WAVES];
 };
+static_assert(TROWS == 16, "xs is read back as four b128 per lane");
 struct __attribute__((aligned(16))) GV(grad_smem) {
     union {
         GV(grad_weights) w;
@@ -34,11 +40,6 @@ struct __attribute__((aligned(16))) GV(grad_smem) {
     double nrm[4];
     double nparts[256];                   // block_grad_norm's S_t (only touched when the clip coefficient is recomputed from the whole gradient)
 };
-#if GRAD_BX
-#define XS(row, k) xs[(row) * 4 + (k)]
-#else
-#define XS(row, k) bufA[(row) * W2S + HID + (k)]
-#endif
 
 template <bool ACTOR>
 __device__ __forceinline__ void GV(grad_body)(GV(grad_smem)& sm, const float* __restrict__ params, const grad_pending_t& pend,
@@ -55,7 +56,8 @@ __device__ __forceinline__ void GV(grad_body)(GV(grad_smem)& sm, const float* __
     // are written at exit.  -59 VALU instructions per actor tile (of ~425) and 16 fewer live registers; same function, another rounding (reference ppo.py:52-59,166-190).
     constexpr bool ANTI = ACTOR;
     constexpr int NHEAD = ANTI ? 1 : NOUT;   // head rows whose gradient is accumulated
-    const int tid = threadIdx.x, lane = tid & 63, wib = tid >> 6;
+    const int tid = threadIdx.x, lane = tid & 63;
+    const int wib = __builtin_amdgcn_readfirstlane(tid >> 6);   // wave-uniform by construction; said so, the tile loop's control and the wave's LDS base are scalar
     const int j = lane & 15, g = lane >> 4;
     const bool pending = pend.grads != nullptr;
     const float* p = (pending ? pend.p_in : params) + BASE;
@@ -220,10 +222,29 @@ __device__ __forceinline__ void GV(grad_body)(GV(grad_smem)& sm, const float* __
         tile = rl.ri * GRAD_WAVES + wib;
         tile_end = n_tiles;
     }
+    // Only the minibatch's LAST tile can be ragged (mb % TROWS rows); the wave that owns it runs it last and apart, with the guarded body.  Every tile below
+    // `lim` is a full one of this wave: the main loop has no row guards.  (tile, stride, tile_end, lim are wave-uniform: scalar registers.)
+    const int full_tiles = mb / TROWS;
+    const int lim = tile_end < full_tiles ? tile_end : full_tiles;
     // ---- input prefetch pipeline: row index two tiles ahead, gathered row one tile ahead ----
+    // The look-ahead past a wave's last full tile is clamped to the last full tile of the MINIBATCH by scalar arithmetic (never past idx[mb - 1]; what it
+    // fetches is not used): the index load is `scalar tile base + 4 j`, no vector arithmetic at all.  The ragged tile fetches its own indices and rows (tile_rid).
+    unsigned j4 = 4u * (unsigned)j;   // (used by full_rid alone: the asm statement there rewrites it in place)
+    auto full_rid = [&](int t) {
+        const int tc = t < full_tiles ? t : full_tiles - 1;
+        gbl_bytes* base = (gbl_bytes*)(idx + (size_t)tc * TROWS);
+        asm volatile("" : "+s"(base), "+v"(j4));   // keeps the scalar tile base and the 32-bit lane offset apart (folded together, and the offset widened outside
+        return *(const __attribute__((address_space(1))) int*)(base + j4);   // the loop, they become a 64-bit vector add per tile)
+    };
     auto tile_rid = [&](int t) { const int row = t * TROWS + j; return idx[row < mb ? row : mb - 1]; };
-    int rid_next = tile_rid(tile + stride);
-    row_in cur = gather_row<ACTOR>(tile_rid(tile), g, observations, actions, log_probs, advantages, returns, values);
+    int rid_next = 0;
+    row_in cur = {0.0f, 0, 0.0f, 0.0f}, nxt = cur;
+    if (tile < lim) {
+        rid_next = full_rid(tile + stride);
+        cur = gather_row<ACTOR>(full_rid(tile), g, observations, actions, log_probs, advantages, returns, values);
+    }
+    const bool only_ragged = tile >= lim && tile < tile_end;   // the ragged tile is this wave's only one: fetched here, under the weight staging, as any first tile
+    if (only_ragged) cur = gather_row<ACTOR>(tile_rid(tile), g, observations, actions, log_probs, advantages, returns, values);
 #ifdef GRAD_STAMPS
     asm volatile("s_memtime %0\n\ts_waitcnt lgkmcnt(0)" : "=s"(pro_t[4]) :: "memory");
 #endif
@@ -278,14 +299,22 @@ __device__ __forceinline__ void GV(grad_body)(GV(grad_smem)& sm, const float* __
     float loss_a = 0.0f, loss_b = 0.0f;  // actor: sum pg, sum entropy; critic: sum max(vl1, vl2)
 
 #if GRAD_BX
-    unsigned short* imgH = W.hb[wib].imgH;
-    unsigned short* imgZ = W.imgZ[wib];
-    float* bufB = W.hb[wib].bufB;
-    float* xs = W.xs[wib];
+    unsigned short* imgH = W.st[wib].hb.imgH;
+    unsigned short* imgZ = W.st[wib].imgZ;
+    float* bufB = W.st[wib].hb.bufB;
 #else
-    float* bufA = W.bufA[wib];
-    float* bufB = W.bufB[wib];
-    float* bufC = W.bufC[wib];
+    float* bufA = W.st[wib].bufA;
+    float* bufB = W.st[wib].bufB;
+    float* bufC = W.st[wib].bufC;
+#endif
+    float* xs = W.st[wib].xs;
+    // read bases of the tile loop's b32 re-reads (lds_read_base): dz1 rows 4k .. 4k + 3 at column `lane`; dz2 / h1 rows 4g .. 4g + 3 at columns j + 16m (252 dwords at most)
+    const lds_f32* rdB[TROWS / 4];
+#pragma unroll
+    for (int k = 0; k < TROWS / 4; ++k) rdB[k] = lds_read_base(bufB + 4 * k * W2S + lane);
+#if !GRAD_BX
+    const lds_f32* rdA = lds_read_base(bufA + 4 * g * W2S + j);
+    const lds_f32* rdC = lds_read_base(bufC + 4 * g * W2S + j);
 #endif
 
 #ifdef GRAD_STAMPS
@@ -294,14 +323,12 @@ __device__ __forceinline__ void GV(grad_body)(GV(grad_smem)& sm, const float* __
     asm volatile("s_memtime %0\n\ts_waitcnt lgkmcnt(0)" : "=s"(stamp_last) :: "memory");
     stamp_t0 = stamp_last;
 #endif
-    int it = 0;
-    for (; tile < tile_end; tile += stride, ++it) {
-        const bool valid = tile * TROWS + j < mb;
-        // issue the next tile's gathers and the index after that; they land while this tile computes
-        const row_in nxt = gather_row<ACTOR>(rid_next, g, observations, actions, log_probs, advantages, returns, values);
-        rid_next = tile_rid(tile + 2 * stride);
-
-        XS(j, g) = cur.x;
+    [[maybe_unused]] int it = 0;   // tiles this wave processed (read by the GRAD_STAMPS build)
+    // One tile.  RAGGED = false: all 16 rows are the minibatch's (no row guards); true: rows at and past mb are masked out of every sum, as ever.
+    auto tile_body = [&](auto ragged, const int t, const row_in& cur) __attribute__((always_inline)) {
+        constexpr bool RAGGED = decltype(ragged)::value;
+        const bool valid = !RAGGED || t * TROWS + j < mb;
+        xs[TROWS * g + j] = cur.x;
         STAMP(0);  // gathers issued
 
         // ---- layer 1: z1^T = W1 x^T + b1 (K = 4 = obs dim: one MFMA per 16-unit tile) ----
@@ -532,12 +559,15 @@ __device__ __forceinline__ void GV(grad_body)(GV(grad_smem)& sm, const float* __
         for (int mt = 0; mt < 4; ++mt)
             *reinterpret_cast<float4*>(bufB + j * W2S + 16 * mt + 4 * g) = make_float4(dz1[mt][0], dz1[mt][1], dz1[mt][2], dz1[mt][3]);
         wave_lds_fence();
+        f32x4 xv[TROWS / 4];   // x[k = lane & 3][row 0..15]
+#pragma unroll
+        for (int q = 0; q < TROWS / 4; ++q) xv[q] = *reinterpret_cast<const f32x4*>(xs + TROWS * (lane & 3) + 4 * q);
 #pragma unroll
         for (int rr = 0; rr < TROWS; rr += 2) {
-            const float z0 = bufB[rr * W2S + lane], z1v = bufB[(rr + 1) * W2S + lane];
+            const float z0 = rdB[rr >> 2][(rr & 3) * W2S], z1v = rdB[(rr + 1) >> 2][((rr + 1) & 3) * W2S];   // dz1[rr][lane], dz1[rr + 1][lane]
             db1 += z0 + z1v;
-            dW1a = mfma4(z0, XS(rr, lane & 3), dW1a);
-            dW1b = mfma4(z1v, XS(rr + 1, lane & 3), dW1b);
+            dW1a = mfma4(z0, xv[rr >> 2][rr & 3], dW1a);
+            dW1b = mfma4(z1v, xv[(rr + 1) >> 2][(rr + 1) & 3], dW1b);
         }
 
         STAMP(8);  // stage dz1 + dW1
@@ -546,10 +576,9 @@ __device__ __forceinline__ void GV(grad_body)(GV(grad_smem)& sm, const float* __
         wave_lds_fence();   // (both images were written phases ago: only reads are left here)
 #pragma unroll
         for (int s = 0; s < 4; ++s) {
-            const int ro = (s + 4 * g) * W2S + j;
-            float a[4], b[4];
+            float a[4], b[4];   // dz2 / h1 [row s + 4g][16m + j]
 #pragma unroll
-            for (int m = 0; m < 4; ++m) { a[m] = bufC[ro + 16 * m]; b[m] = bufA[ro + 16 * m]; db2[m] += a[m]; }
+            for (int m = 0; m < 4; ++m) { a[m] = rdC[s * W2S + 16 * m]; b[m] = rdA[s * W2S + 16 * m]; db2[m] += a[m]; }
 #pragma unroll
             for (int mo = 0; mo < 4; ++mo)
 #pragma unroll
@@ -557,8 +586,24 @@ __device__ __forceinline__ void GV(grad_body)(GV(grad_smem)& sm, const float* __
         }
 #endif
         STAMP(9);  // dW2
+    };
+    // a full tile: issue the next tile's gathers into `n` and the index after that (they land while this tile computes), then compute on `c`
+    auto full_step = [&](const row_in& c, row_in& n, const int t) __attribute__((always_inline)) {
+        n = gather_row<ACTOR>(rid_next, g, observations, actions, log_probs, advantages, returns, values);
+        rid_next = full_rid(t + 2 * stride);
+        tile_body(grad_tag<false>{}, t, c);
+        ++it;
+    };
+    // main loop over the full tiles, then the ragged one.  (Two tiles per trip with `cur` and `nxt` exchanging roles would save the hand-over's register copies,
+    // 3 - 4 per tile; that form spilled — 1 VGPR here, 24 in the bf16x3 instantiation — and was dropped: docs/LEDGER.md.)
+    for (; tile < lim; tile += stride) {
+        full_step(cur, nxt, tile);
         cur = nxt;
-        STAMP(10);  // wait for the prefetched row
+    }
+    if (tile < tile_end) {   // here tile == full_tiles
+        if (!only_ragged) cur = gather_row<ACTOR>(tile_rid(tile), g, observations, actions, log_probs, advantages, returns, values);
+        tile_body(grad_tag<true>{}, tile, cur);
+        ++it;
     }
 #ifdef GRAD_STAMPS
     if (lane == 0) {  // diagnostic build: the slabs behind GRAD_MAX_BLOCKS / 2 (unused by grids of <= 512 blocks) receive the stamps
@@ -699,5 +744,3 @@ GV(grad_kernel)(const float* __restrict__ params, grad_pending_t pend, const flo
         GV(grad_body)<false>(sm, params, pend, observations, actions, log_probs, advantages, returns, values, idx, mb, adv_sums, clip_coef,
                          ent_coef, vf_coef, invn, part, vb, rl);
 }
-
-#undef XS

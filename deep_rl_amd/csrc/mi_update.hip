@@ -448,24 +448,43 @@ __host__ __device__ inline grad_role_t grad_role(unsigned vb, int n_blocks) {
 }
 __host__ __device__ inline int grad_slab(int role, int ri) { return 2 * ri + role; }   // inverse: the slab of workgroup ri of a role
 
+// A loop-invariant LDS read base the compiler keeps in its register: seen through, `base + constant` is re-derived by a v_add_u32 inside the tile loop for every
+// ds_read2_b32 pair whose offsets leave the instruction's 8-bit range (255 dwords from the base).
+typedef __attribute__((address_space(3))) float lds_f32;
+typedef const __attribute__((address_space(1))) char gbl_bytes;   // (an address that passes through an asm statement keeps its address space only in its type)
+__device__ __forceinline__ const lds_f32* lds_read_base(const float* p) {
+    const lds_f32* q = (const lds_f32*)p;
+    asm volatile("" : "+v"(q));
+    return q;
+}
+template <bool B> struct grad_tag{ static constexpr bool value = B; };   // compile-time switch of grad_body's tile lambda: ragged (guarded) or full tile
+
 struct row_in {
     float x;          // observation component g of the row (lane (j,g))
     int act;
     float f0, f1;     // actor: old log-prob, advantage; critic: return, old value
 };
 
+// Byte offsets are 32-bit unsigned (GRAD_MAX_ROWS: a storage row's 16 observation bytes stay below 4 GiB), so every load is `scalar base + 32-bit lane offset`:
+// one shift per array in place of a 64-bit address chain (the arrays' bases are kernel arguments = scalar registers).
+#define GRAD_MAX_ROWS (1 << 28)
+template <typename T>
+__device__ __forceinline__ T load_at(const void* __restrict__ base, unsigned byte_off) {
+    return *reinterpret_cast<const T*>(reinterpret_cast<const char*>(base) + byte_off);
+}
 template <bool ACTOR>
 __device__ __forceinline__ row_in gather_row(int rid, int g, const float* __restrict__ observations, const int64_t* __restrict__ actions,
                                              const float* __restrict__ log_probs, const float* __restrict__ advantages,
                                              const float* __restrict__ returns, const float* __restrict__ values) {
     row_in r;
-    r.x = observations[4 * (size_t)rid + g];
+    const unsigned urid = (unsigned)rid;
+    r.x = load_at<float>(observations, 16u * urid + 4u * (unsigned)g);
     if constexpr (ACTOR) {
-        r.act = reinterpret_cast<const int*>(actions)[2 * (size_t)rid];  // low dword of the int64 (0 or 1)
-        r.f0 = log_probs[rid]; r.f1 = advantages[rid];
+        r.act = load_at<int>(actions, 8u * urid);  // low dword of the int64 (0 or 1)
+        r.f0 = load_at<float>(log_probs, 4u * urid); r.f1 = load_at<float>(advantages, 4u * urid);
     } else {
         r.act = 0;
-        r.f0 = returns[rid]; r.f1 = values[rid];
+        r.f0 = load_at<float>(returns, 4u * urid); r.f1 = load_at<float>(values, 4u * urid);
     }
     return r;
 }
@@ -690,8 +709,8 @@ extern "C" int mi_ppo_minibatch_grad(const float* params, const float* observati
                                      float* loss_terms, void* stream) {
     MI_CHECK_ARG(params && observations && actions && log_probs && advantages && returns && values && idx && adv_sums, "NULL input");
     MI_CHECK_ARG(workspace && grads, "NULL workspace/grads");
-    MI_CHECK_ARG(mb > 0, "mb must be positive");
-    return ppo_grad_launch(params, no_pending(), observations, actions, log_probs, advantages, returns, values, idx, mb, adv_sums, clip_coef, ent_coef,
+    MI_CHECK_ARG(mb > 0 && mb <= GRAD_MAX_ROWS, "mb must be positive and at most 2^28");   // idx[] holds distinct storage rows < 2^28 (32-bit gather offsets)
+    return ppo_grad_launch(params, no_pending(),observations, actions, log_probs, advantages, returns, values, idx, mb, adv_sums, clip_coef, ent_coef,
                            vf_coef, inv_count, workspace, grads, loss_terms, (hipStream_t)stream);
 }
 
@@ -888,6 +907,7 @@ static int ppo_update_impl(void* handle, const mi_ppo_buffers_t* b, const mi_ppo
     mi_env* e = (mi_env*)handle;
     const int N = e->n, B = hp->T * N;
     MI_CHECK_ARG(B % hp->n_minibatch == 0, "T*N must be divisible by n_minibatch");
+    MI_CHECK_ARG((long long)(hp->T + 1) * N <= GRAD_MAX_ROWS, "(T+1)*N exceeds 2^28 storage rows (the gradient kernel gathers with 32-bit byte offsets)");
     const int mb = B / hp->n_minibatch;
     const bool fused = (mb % PS_PER_BLOCK) == 0;  // perm + stats in one pass; their fp64 accumulators are zeroed by the rollout launch
     // P2P carrier: grad_reduce_kernel itself exchanges {gradient, loss terms} (no launch per all-reduce) and its block sums of squares are those of the ALL-REDUCED
