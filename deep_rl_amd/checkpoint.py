@@ -14,6 +14,7 @@ from .c51_engine import C51Engine
 from .iqn_engine import IQNEngine
 from .qrdqn_engine import QRDQNEngine
 from .ddqn_engine import DoubleDQNEngine
+from .pdd_engine import PDDDQNEngine
 from .dqn_engine import DQNEngine, DuelingDQNEngine, PERDQNEngine
 from .engine import PPOEngine
 from .reinforce_engine import ReinforceEngine
@@ -47,7 +48,12 @@ def _opt_restore(o, z, prefix):
 
 def _target_net(engine):
     """the target network of an off-policy engine (C51Engine's `target` is its method for the projected targets)"""
-    return engine.target_network if isinstance(engine, (C51Engine, IQNEngine, QRDQNEngine, DoubleDQNEngine)) else engine.target
+    return engine.target_network if isinstance(engine, (C51Engine, IQNEngine, QRDQNEngine, DoubleDQNEngine, PDDDQNEngine)) else engine.target
+
+
+def _has_priorities(engine):
+    """PERDQNEngine, and PDDDQNEngine in its prioritized mode: a priorities ring and the running max_priority beside the replay ring"""
+    return isinstance(engine, PERDQNEngine) or (isinstance(engine, PDDDQNEngine) and engine.prioritized)
 
 
 def state_dict(engine, include_replay=True):
@@ -57,10 +63,10 @@ def state_dict(engine, include_replay=True):
           "env_id_base": np.int64(env.env_id_base), "env_blob": _env_blob(env), "observation": engine.observation}
     if isinstance(engine, (PPOEngine, ReinforceEngine)):   # REINFORCE keeps nothing across updates but the env counters, the parameters and Adam's state
         st.update(params=engine.agent.flat, update_index=np.int64(engine.update_index), **_opt_state(engine.optimizer, "opt_"))
-    elif isinstance(engine, (DQNEngine, C51Engine, IQNEngine, QRDQNEngine, DoubleDQNEngine)):   # C51: the same ring, two networks, one Adam
+    elif isinstance(engine, (DQNEngine, C51Engine, IQNEngine, QRDQNEngine, DoubleDQNEngine, PDDDQNEngine)):   # C51: the same ring, two networks, one Adam
         st.update(params=engine.q.flat, target=_target_net(engine).flat, global_step=np.int64(engine.global_step), update_index=np.int64(engine.update_index),
                   **_opt_state(engine.optimizer, "opt_"))
-        if isinstance(engine, PERDQNEngine):
+        if _has_priorities(engine):
             st.update(max_priority=engine.max_priority)
             if include_replay:
                 st.update(priorities=engine.priorities)
@@ -115,7 +121,7 @@ def load(path, engine):
     _env_restore(env, z["env_blob"])
     if isinstance(engine, (PPOEngine, ReinforceEngine)):
         _check_shape(z, "params", engine.agent.flat.shape)
-    elif isinstance(engine, (DQNEngine, C51Engine, IQNEngine, QRDQNEngine, DoubleDQNEngine)):
+    elif isinstance(engine, (DQNEngine, C51Engine, IQNEngine, QRDQNEngine, DoubleDQNEngine, PDDDQNEngine)):
         _check_shape(z, "params", engine.q.flat.shape); _check_shape(z, "target", _target_net(engine).flat.shape)
     else:
         _check_shape(z, "actor", engine.actor.flat.shape); _check_shape(z, "q", engine.q_flat.shape); _check_shape(z, "q_target", engine.qt_flat.shape)
@@ -125,13 +131,13 @@ def load(path, engine):
     engine.observation = t("observation")
     if isinstance(engine, (PPOEngine, ReinforceEngine)):
         engine.agent.flat.copy_(t("params")); engine.update_index = int(z["update_index"]); _opt_restore(engine.optimizer, z, "opt_")
-    elif isinstance(engine, (DQNEngine, C51Engine, IQNEngine, QRDQNEngine, DoubleDQNEngine)):
+    elif isinstance(engine, (DQNEngine, C51Engine, IQNEngine, QRDQNEngine, DoubleDQNEngine, PDDDQNEngine)):
         engine.q.flat.copy_(t("params")); _target_net(engine).flat.copy_(t("target"))
         if isinstance(engine, DuelingDQNEngine):
             engine.q.repack(); engine.target.repack()
         engine.global_step, engine.update_index = int(z["global_step"]), int(z["update_index"])
         _opt_restore(engine.optimizer, z, "opt_")
-        if isinstance(engine, PERDQNEngine):
+        if _has_priorities(engine):
             engine.max_priority.copy_(t("max_priority"))
             if "priorities" in z:
                 engine.priorities.copy_(t("priorities"))
