@@ -173,7 +173,8 @@ def target(target_params, X_next, rewards, terminated, next_taus, tau_dashes, ga
 
 def quantile_huber(current, tgt, taus, dtype=f32):
     """loss and dcurrent of iqn.py:281-289 (kappa = 1) from current [B][64], target [B][64], taus [B][64]; f32: the header's order (rows added ascending)"""
-    cur = np.asarray(current, f32).astype(dtype); tg = np.asarray(tgt, f32).astype(dtype); tau = np.asarray(taus, f32).astype(dtype)
+    inp = f32 if dtype is f32 else np.float64   # float64: current and target as the float64 forward formed them, not rounded to f32 on the way in (taus are f32 inputs)
+    cur = np.asarray(current, inp).astype(dtype); tg = np.asarray(tgt, inp).astype(dtype); tau = np.asarray(taus, f32).astype(dtype)
     B = cur.shape[0]
     d = (tg[:, None, :] - cur[:, :, None]).astype(dtype)   # [b][i][j]
     ad = np.abs(d)
