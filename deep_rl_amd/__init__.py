@@ -21,6 +21,7 @@ from .iqn_engine import IQNEngine  # noqa: F401  (libmirl_iqn.so itself loads on
 from .qrdqn_engine import QRDQNEngine  # noqa: F401  (libmirl_qr.so itself loads on first use)
 from .ddqn_engine import DoubleDQNEngine  # noqa: F401  (libmirl_ddqn.so itself loads on first use)
 from .pdd_engine import PDDDQNEngine  # noqa: F401  (libmirl_pdd.so itself loads on first use)
+from .nstep_engine import NStepDQNEngine  # noqa: F401  (libmirl_nstep.so itself loads on first use)
 
 __all__ = ["make", "CartPoleVecEnv", "ActorCritic", "QNetwork", "layer_init", "ClipAdam", "PPOEngine", "DQNEngine",
-           "DuelingQNetwork", "DuelingDQNEngine", "PERDQNEngine", "PendulumVecEnv", "SoftQNetwork", "Actor", "Adam", "SACEngine", "DropoutPolicy", "ReinforceEngine", "C51QNetwork", "C51Engine", "FeaturesExtractor", "CosineEmbeddingNetwork", "QuantileNetwork", "iqn_forward", "IQNEngine", "QRQNetwork", "QRDQNEngine", "DoubleDQNEngine", "PDDDQNEngine", "pack", "set_contraction", "get_contraction"]
+           "DuelingQNetwork", "DuelingDQNEngine", "PERDQNEngine", "PendulumVecEnv", "SoftQNetwork", "Actor", "Adam", "SACEngine", "DropoutPolicy", "ReinforceEngine", "C51QNetwork", "C51Engine", "FeaturesExtractor", "CosineEmbeddingNetwork", "QuantileNetwork", "iqn_forward", "IQNEngine", "QRQNetwork", "QRDQNEngine", "DoubleDQNEngine", "PDDDQNEngine", "NStepDQNEngine", "pack", "set_contraction", "get_contraction"]

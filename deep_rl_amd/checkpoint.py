@@ -15,6 +15,7 @@ from .iqn_engine import IQNEngine
 from .qrdqn_engine import QRDQNEngine
 from .ddqn_engine import DoubleDQNEngine
 from .pdd_engine import PDDDQNEngine
+from .nstep_engine import NStepDQNEngine
 from .dqn_engine import DQNEngine, DuelingDQNEngine, PERDQNEngine
 from .engine import PPOEngine
 from .reinforce_engine import ReinforceEngine
@@ -66,6 +67,8 @@ def state_dict(engine, include_replay=True):
     elif isinstance(engine, (DQNEngine, C51Engine, IQNEngine, QRDQNEngine, DoubleDQNEngine, PDDDQNEngine)):   # C51: the same ring, two networks, one Adam
         st.update(params=engine.q.flat, target=_target_net(engine).flat, global_step=np.int64(engine.global_step), update_index=np.int64(engine.update_index),
                   **_opt_state(engine.optimizer, "opt_"))
+        if isinstance(engine, NStepDQNEngine):   # (a PDDDQNEngine: everything above and below applies) the length of its walks is part of what it computes
+            st.update(n_step=np.int64(engine.n_step))
         if _has_priorities(engine):
             st.update(max_priority=engine.max_priority)
             if include_replay:
@@ -116,6 +119,8 @@ def load(path, engine):
     if str(z["kind"]) != type(engine).__name__ or int(z["num_envs"]) != env.num_envs or int(z["seed"]) != env._seed or int(z["env_id_base"]) != env.env_id_base:
         raise N.MiError("checkpoint: written for %s with (num_envs, seed, env_id_base) = (%d, %d, %d); this engine is %s (%d, %d, %d)" % (
             z["kind"], z["num_envs"], z["seed"], z["env_id_base"], type(engine).__name__, env.num_envs, env._seed, env.env_id_base))
+    if isinstance(engine, NStepDQNEngine) and ("n_step" not in z or int(z["n_step"]) != engine.n_step):
+        raise N.MiError("checkpoint: written with n_step = %s, this engine has n_step = %d" % (z.get("n_step"), engine.n_step))
     dev = engine.device
     t = lambda name: torch.from_numpy(z[name]).to(dev)   # noqa: E731
     _env_restore(env, z["env_blob"])
