@@ -11,6 +11,7 @@ from ._native import set_contraction, get_contraction  # noqa: F401
 from .envs import make, CartPoleVecEnv, PendulumVecEnv  # noqa: F401
 from .agent import ActorCritic, QNetwork, DuelingQNetwork, SoftQNetwork, Actor, DropoutPolicy, C51QNetwork, QRQNetwork, layer_init, pack  # noqa: F401
 from .agent import FeaturesExtractor, CosineEmbeddingNetwork, QuantileNetwork, iqn_forward  # noqa: F401
+from .agent import NoisyLinear, NoisyDuelingQNetwork  # noqa: F401
 from .optim import ClipAdam, Adam  # noqa: F401
 from .engine import PPOEngine  # noqa: F401
 from .dqn_engine import DQNEngine, DuelingDQNEngine, PERDQNEngine  # noqa: F401
@@ -22,6 +23,7 @@ from .qrdqn_engine import QRDQNEngine  # noqa: F401  (libmirl_qr.so itself loads
 from .ddqn_engine import DoubleDQNEngine  # noqa: F401  (libmirl_ddqn.so itself loads on first use)
 from .pdd_engine import PDDDQNEngine  # noqa: F401  (libmirl_pdd.so itself loads on first use)
 from .nstep_engine import NStepDQNEngine  # noqa: F401  (libmirl_nstep.so itself loads on first use)
+from .noisy_engine import NoisyDQNEngine  # noqa: F401  (libmirl_noisy.so itself loads on first use)
 
 __all__ = ["make", "CartPoleVecEnv", "ActorCritic", "QNetwork", "layer_init", "ClipAdam", "PPOEngine", "DQNEngine",
-           "DuelingQNetwork", "DuelingDQNEngine", "PERDQNEngine", "PendulumVecEnv", "SoftQNetwork", "Actor", "Adam", "SACEngine", "DropoutPolicy", "ReinforceEngine", "C51QNetwork", "C51Engine", "FeaturesExtractor", "CosineEmbeddingNetwork", "QuantileNetwork", "iqn_forward", "IQNEngine", "QRQNetwork", "QRDQNEngine", "DoubleDQNEngine", "PDDDQNEngine", "NStepDQNEngine", "pack", "set_contraction", "get_contraction"]
+           "DuelingQNetwork", "DuelingDQNEngine", "PERDQNEngine", "PendulumVecEnv", "SoftQNetwork", "Actor", "Adam", "SACEngine", "DropoutPolicy", "ReinforceEngine", "C51QNetwork", "C51Engine", "FeaturesExtractor", "CosineEmbeddingNetwork", "QuantileNetwork", "iqn_forward", "IQNEngine", "QRQNetwork", "QRDQNEngine", "DoubleDQNEngine", "PDDDQNEngine", "NStepDQNEngine", "NoisyLinear", "NoisyDuelingQNetwork", "NoisyDQNEngine", "pack", "set_contraction", "get_contraction"]

@@ -440,3 +440,50 @@ def iqn_forward(flat, observation, taus):
     q = torch.empty((n, 2), dtype=torch.float32, device=dev)
     K.check(K.lib().mi_iqn_forward(N.ptr(flat), N.ptr(obs), N.ptr(tau), n, k, N.ptr(quant), N.ptr(q), N.stream_ptr(dev)), "mi_iqn_forward")
     return quant.reshape(*lead, k, 2), q.reshape(*lead, 2)
+
+
+class NoisyLinear(nn.Module):
+    """A factorised-Gaussian noisy linear layer (Fortunato et al. 2018, as Rainbow uses it): weight = weight_mu + weight_sigma * eps_w, bias = bias_mu +
+    bias_sigma * eps_b.  mu ~ U(+-1 / sqrt(in_features)), sigma = sigma_0 / sqrt(in_features).  The module holds the DISTRIBUTION only; the draws are the
+    kernels' (include/mi_noisy.h), and ``forward`` is the mean layer."""
+
+    def __init__(self, in_features, out_features, sigma_0=0.5):
+        super().__init__()
+        self.in_features, self.out_features, self.sigma_0 = int(in_features), int(out_features), float(sigma_0)
+        bound = 1.0 / np.sqrt(self.in_features)
+        self.weight_mu = nn.Parameter(torch.empty(self.out_features, self.in_features).uniform_(-bound, bound))
+        self.bias_mu = nn.Parameter(torch.empty(self.out_features).uniform_(-bound, bound))
+        self.weight_sigma = nn.Parameter(torch.full((self.out_features, self.in_features), self.sigma_0 / np.sqrt(self.in_features)))
+        self.bias_sigma = nn.Parameter(torch.full((self.out_features,), self.sigma_0 / np.sqrt(self.in_features)))
+
+    def forward(self, input):
+        return nn.functional.linear(input, self.weight_mu, self.bias_mu)
+
+
+class NoisyDuelingQNetwork(_FlatModule):
+    """DuelingQNetwork whose value and advantage streams are ``NoisyLinear``s: 11,274 floats (include/mi_noisy.h).  ``flat`` is DuelingQNetwork's 11,019-float
+    vector with the streams' means in the place of their weights, then the 255 sigmas in the same order — all mu, then all sigma — which is NOT the modules'
+    registration order, so ``parameters()`` is overridden to give the flat order (what ``_finish``, ``_bind_flat`` and an optimizer walk).  The torso is plain.
+    ``forward`` is the mean network on CPU parameters; on the device the values come from NoisyDQNEngine.forward."""
+
+    def __init__(self, env, device=None, sigma_0=0.5):
+        super().__init__()
+        from . import _native_nz as K
+        obs_dim = int(np.prod(env.observation_space.shape))
+        if obs_dim != 4 or env.action_space.n != 2:
+            raise N.MiError("the HIP kernels are specialised for CartPole (obs 4, actions 2)")
+        self.feauture_layer = nn.Sequential(nn.Linear(obs_dim, 120), nn.ReLU(), nn.Linear(120, 84), nn.ReLU())
+        self.value_stream = NoisyLinear(84, 1, sigma_0)
+        self.advantage_stream = NoisyLinear(84, env.action_space.n, sigma_0)
+        self._finish(env, device, K.NPARAMS)
+
+    def parameters(self, recurse=True):
+        v, a = self.value_stream, self.advantage_stream
+        yield from self.feauture_layer.parameters()
+        yield from (v.weight_mu, v.bias_mu, a.weight_mu, a.bias_mu, v.weight_sigma, v.bias_sigma, a.weight_sigma, a.bias_sigma)
+
+    def forward(self, observation):
+        _cpu_only(self)
+        h = self.feauture_layer(observation.to(torch.float32))
+        values, advantages = self.value_stream(h), self.advantage_stream(h)
+        return values + (advantages - advantages.mean(dim=-1, keepdim=True))

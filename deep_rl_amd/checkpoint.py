@@ -16,6 +16,7 @@ from .qrdqn_engine import QRDQNEngine
 from .ddqn_engine import DoubleDQNEngine
 from .pdd_engine import PDDDQNEngine
 from .nstep_engine import NStepDQNEngine
+from .noisy_engine import NoisyDQNEngine
 from .dqn_engine import DQNEngine, DuelingDQNEngine, PERDQNEngine
 from .engine import PPOEngine
 from .reinforce_engine import ReinforceEngine
@@ -64,7 +65,9 @@ def state_dict(engine, include_replay=True):
           "env_id_base": np.int64(env.env_id_base), "env_blob": _env_blob(env), "observation": engine.observation}
     if isinstance(engine, (PPOEngine, ReinforceEngine)):   # REINFORCE keeps nothing across updates but the env counters, the parameters and Adam's state
         st.update(params=engine.agent.flat, update_index=np.int64(engine.update_index), **_opt_state(engine.optimizer, "opt_"))
-    elif isinstance(engine, (DQNEngine, C51Engine, IQNEngine, QRDQNEngine, DoubleDQNEngine, PDDDQNEngine)):   # C51: the same ring, two networks, one Adam
+    # NoisyDQNEngine (tested ahead of its bases NStepDQNEngine and PDDDQNEngine) saves nothing of its own: its noise is keyed by the env's step counters and by
+    # update_index, which are saved already, and its 11,274-float vectors are `params` / `target` as for every other engine
+    elif isinstance(engine, (NoisyDQNEngine, DQNEngine, C51Engine, IQNEngine, QRDQNEngine, DoubleDQNEngine, PDDDQNEngine)):   # C51: the same ring, two networks, one Adam
         st.update(params=engine.q.flat, target=_target_net(engine).flat, global_step=np.int64(engine.global_step), update_index=np.int64(engine.update_index),
                   **_opt_state(engine.optimizer, "opt_"))
         if isinstance(engine, NStepDQNEngine):   # (a PDDDQNEngine: everything above and below applies) the length of its walks is part of what it computes
