@@ -11,7 +11,7 @@ from ._native import set_contraction, get_contraction  # noqa: F401
 from .envs import make, CartPoleVecEnv, PendulumVecEnv  # noqa: F401
 from .agent import ActorCritic, QNetwork, DuelingQNetwork, SoftQNetwork, Actor, DropoutPolicy, C51QNetwork, QRQNetwork, layer_init, pack  # noqa: F401
 from .agent import FeaturesExtractor, CosineEmbeddingNetwork, QuantileNetwork, iqn_forward  # noqa: F401
-from .agent import NoisyLinear, NoisyDuelingQNetwork  # noqa: F401
+from .agent import NoisyLinear, NoisyDuelingQNetwork, RainbowQNetwork  # noqa: F401
 from .optim import ClipAdam, Adam  # noqa: F401
 from .engine import PPOEngine  # noqa: F401
 from .dqn_engine import DQNEngine, DuelingDQNEngine, PERDQNEngine  # noqa: F401
@@ -24,6 +24,7 @@ from .ddqn_engine import DoubleDQNEngine  # noqa: F401  (libmirl_ddqn.so itself 
 from .pdd_engine import PDDDQNEngine  # noqa: F401  (libmirl_pdd.so itself loads on first use)
 from .nstep_engine import NStepDQNEngine  # noqa: F401  (libmirl_nstep.so itself loads on first use)
 from .noisy_engine import NoisyDQNEngine  # noqa: F401  (libmirl_noisy.so itself loads on first use)
+from .rainbow_engine import RainbowEngine  # noqa: F401  (libmirl_rainbow.so itself loads on first use)
 
 __all__ = ["make", "CartPoleVecEnv", "ActorCritic", "QNetwork", "layer_init", "ClipAdam", "PPOEngine", "DQNEngine",
-           "DuelingQNetwork", "DuelingDQNEngine", "PERDQNEngine", "PendulumVecEnv", "SoftQNetwork", "Actor", "Adam", "SACEngine", "DropoutPolicy", "ReinforceEngine", "C51QNetwork", "C51Engine", "FeaturesExtractor", "CosineEmbeddingNetwork", "QuantileNetwork", "iqn_forward", "IQNEngine", "QRQNetwork", "QRDQNEngine", "DoubleDQNEngine", "PDDDQNEngine", "NStepDQNEngine", "NoisyLinear", "NoisyDuelingQNetwork", "NoisyDQNEngine", "pack", "set_contraction", "get_contraction"]
+           "DuelingQNetwork", "DuelingDQNEngine", "PERDQNEngine", "PendulumVecEnv", "SoftQNetwork", "Actor", "Adam", "SACEngine", "DropoutPolicy", "ReinforceEngine", "C51QNetwork", "C51Engine", "FeaturesExtractor", "CosineEmbeddingNetwork", "QuantileNetwork", "iqn_forward", "IQNEngine", "QRQNetwork", "QRDQNEngine", "DoubleDQNEngine", "PDDDQNEngine", "NStepDQNEngine", "NoisyLinear", "NoisyDuelingQNetwork", "NoisyDQNEngine", "RainbowQNetwork", "RainbowEngine", "pack", "set_contraction", "get_contraction"]

@@ -487,3 +487,40 @@ class NoisyDuelingQNetwork(_FlatModule):
         h = self.feauture_layer(observation.to(torch.float32))
         values, advantages = self.value_stream(h), self.advantage_stream(h)
         return values + (advantages - advantages.mean(dim=-1, keepdim=True))
+
+
+class RainbowQNetwork(_FlatModule):
+    """Rainbow's network: the 4 -> 120 -> 84 torso and two ``NoisyLinear`` streams that produce 51 atoms each — value [51], advantage [2 * 51] — combined by the
+    dueling rule per atom and normalised by a softmax per action: 36,774 floats (include/mi_rainbow.h).  ``flat`` is all mu, then all sigma (``parameters()`` is
+    overridden to give that order, as NoisyDuelingQNetwork does).  ``forward`` is the MEAN network's action values on CPU parameters under the support
+    ``(v_min, v_max)``; on the device the distributions and values come from RainbowEngine.forward."""
+
+    def __init__(self, env, device=None, sigma_0=0.5, n_atoms=51, v_min=0.0, v_max=100.0):
+        super().__init__()
+        from . import _native_rb as K
+        obs_dim = int(np.prod(env.observation_space.shape))
+        if obs_dim != 4 or env.action_space.n != 2:
+            raise N.MiError("the HIP kernels are specialised for CartPole (obs 4, actions 2)")
+        if int(n_atoms) != K.N_ATOMS:
+            raise N.MiError("the Rainbow kernels are specialised for n_atoms = %d; got %r" % (K.N_ATOMS, n_atoms))
+        self.n_atoms, self.v_min, self.v_max = int(n_atoms), float(v_min), float(v_max)
+        self.feauture_layer = nn.Sequential(nn.Linear(obs_dim, 120), nn.ReLU(), nn.Linear(120, 84), nn.ReLU())
+        self.value_stream = NoisyLinear(84, self.n_atoms, sigma_0)
+        self.advantage_stream = NoisyLinear(84, env.action_space.n * self.n_atoms, sigma_0)
+        self._finish(env, device, K.NPARAMS)
+
+    def parameters(self, recurse=True):
+        v, a = self.value_stream, self.advantage_stream
+        yield from self.feauture_layer.parameters()
+        yield from (v.weight_mu, v.bias_mu, a.weight_mu, a.bias_mu, v.weight_sigma, v.bias_sigma, a.weight_sigma, a.bias_sigma)
+
+    def get_probs(self, observation):
+        _cpu_only(self)
+        h = self.feauture_layer(observation.to(torch.float32))
+        values = self.value_stream(h)[..., None, :]
+        advantages = self.advantage_stream(h).unflatten(-1, (2, self.n_atoms))
+        return torch.softmax(values + (advantages - advantages.mean(dim=-2, keepdim=True)), dim=-1)
+
+    def forward(self, observation):
+        atoms = torch.linspace(self.v_min, self.v_max, self.n_atoms)
+        return (self.get_probs(observation) * atoms).sum(-1)

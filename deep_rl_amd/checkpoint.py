@@ -17,6 +17,7 @@ from .ddqn_engine import DoubleDQNEngine
 from .pdd_engine import PDDDQNEngine
 from .nstep_engine import NStepDQNEngine
 from .noisy_engine import NoisyDQNEngine
+from .rainbow_engine import RainbowEngine
 from .dqn_engine import DQNEngine, DuelingDQNEngine, PERDQNEngine
 from .engine import PPOEngine
 from .reinforce_engine import ReinforceEngine
@@ -67,7 +68,8 @@ def state_dict(engine, include_replay=True):
         st.update(params=engine.agent.flat, update_index=np.int64(engine.update_index), **_opt_state(engine.optimizer, "opt_"))
     # NoisyDQNEngine (tested ahead of its bases NStepDQNEngine and PDDDQNEngine) saves nothing of its own: its noise is keyed by the env's step counters and by
     # update_index, which are saved already, and its 11,274-float vectors are `params` / `target` as for every other engine
-    elif isinstance(engine, (NoisyDQNEngine, DQNEngine, C51Engine, IQNEngine, QRDQNEngine, DoubleDQNEngine, PDDDQNEngine)):   # C51: the same ring, two networks, one Adam
+    # RainbowEngine (a NoisyDQNEngine, named ahead of its bases) likewise: the support is the caller's constructor argument, like gamma
+    elif isinstance(engine, (RainbowEngine, NoisyDQNEngine, DQNEngine, C51Engine, IQNEngine, QRDQNEngine, DoubleDQNEngine, PDDDQNEngine)):   # C51: the same ring, two networks, one Adam
         st.update(params=engine.q.flat, target=_target_net(engine).flat, global_step=np.int64(engine.global_step), update_index=np.int64(engine.update_index),
                   **_opt_state(engine.optimizer, "opt_"))
         if isinstance(engine, NStepDQNEngine):   # (a PDDDQNEngine: everything above and below applies) the length of its walks is part of what it computes
