@@ -26,5 +26,16 @@ from .nstep_engine import NStepDQNEngine  # noqa: F401  (libmirl_nstep.so itself
 from .noisy_engine import NoisyDQNEngine  # noqa: F401  (libmirl_noisy.so itself loads on first use)
 from .rainbow_engine import RainbowEngine  # noqa: F401  (libmirl_rainbow.so itself loads on first use)
 
+
+def __getattr__(name):
+    """``deep_rl_amd.evaluate`` (greedy policy evaluation, libmirl_eval.so) is imported on first use; the module is callable: ``deep_rl_amd.evaluate(engine)``"""
+    if name in ("evaluate", "EvalResult"):
+        import importlib
+
+        mod = importlib.import_module(".evaluate", __name__)
+        return mod if name == "evaluate" else mod.EvalResult
+    raise AttributeError("module %r has no attribute %r" % (__name__, name))
+
+
 __all__ = ["make", "CartPoleVecEnv", "ActorCritic", "QNetwork", "layer_init", "ClipAdam", "PPOEngine", "DQNEngine",
-           "DuelingQNetwork", "DuelingDQNEngine", "PERDQNEngine", "PendulumVecEnv", "SoftQNetwork", "Actor", "Adam", "SACEngine", "DropoutPolicy", "ReinforceEngine", "C51QNetwork", "C51Engine", "FeaturesExtractor", "CosineEmbeddingNetwork", "QuantileNetwork", "iqn_forward", "IQNEngine", "QRQNetwork", "QRDQNEngine", "DoubleDQNEngine", "PDDDQNEngine", "NStepDQNEngine", "NoisyLinear", "NoisyDuelingQNetwork", "NoisyDQNEngine", "RainbowQNetwork", "RainbowEngine", "pack", "set_contraction", "get_contraction"]
+           "DuelingQNetwork", "DuelingDQNEngine", "PERDQNEngine", "PendulumVecEnv", "SoftQNetwork", "Actor", "Adam", "SACEngine", "DropoutPolicy", "ReinforceEngine", "C51QNetwork", "C51Engine", "FeaturesExtractor", "CosineEmbeddingNetwork", "QuantileNetwork", "iqn_forward", "IQNEngine", "QRQNetwork", "QRDQNEngine", "DoubleDQNEngine", "PDDDQNEngine", "NStepDQNEngine", "NoisyLinear", "NoisyDuelingQNetwork", "NoisyDQNEngine", "RainbowQNetwork", "RainbowEngine", "pack", "set_contraction", "get_contraction", "evaluate", "EvalResult"]
