@@ -116,7 +116,7 @@ __device__ __forceinline__ float ev_atom(const ev_support& z, int j) { return z.
 // ts_row — gives both action values to every thread.  Behind values() sm.h2 / sm.y / sm.q are next written behind at least two barriers of the next ts_row.
 template <int KIND> struct ev_net;
 
-template <> struct ev_net<MI_EV_DUELING> {   // mi_pdd.hip: pd_load_head, pd_values
+template <> struct ev_net<MI_EV_DUELING> {   // mi_dueling.h: du_load_head, du_values
     __device__ __forceinline__ void load(const float* __restrict__ P, ev_smem& sm, const ev_support&, int t) {
         if (t < EV_DU_N) sm.hd[t] = P[EV_HEAD + t];
         __syncthreads();

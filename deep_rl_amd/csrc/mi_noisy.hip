@@ -6,41 +6,36 @@
 // Philox calls and two Box-Muller values; the output factors are recomputed redundantly across threads) and writes mu_t + sigma_t * eps_t into sm.hd, so forming the
 // effective head needs no LDS exchange and no barrier of its own — the torso's three barriers publish it as they publish a loaded head.
 //   nz_act_kernel      rg_act_loop as it is, instantiated with and without the noise (without it the kernel is pdd_act_kernel).  policy.greedy forms a fresh head
-//                      per greedy env step ahead of pd_torso_rows.  The acting launch uses only the online network, so the two copies sm.hd[0] / sm.hd[1] ALTERNATE between greedy steps: step k writes the copy step k - 2 read, and every wave has
-//                      left step k - 2's pd_values before any passes the three barriers of step k - 1.  No barrier is added.
+//                      per greedy env step ahead of du_torso_rows.  The acting launch uses only the online network, so the two copies sm.hd[0] / sm.hd[1] ALTERNATE between greedy steps: step k writes the copy step k - 2 read, and every wave has
+//                      left step k - 2's du_values before any passes the three barriers of step k - 1.  No barrier is added.
 //   nz_forward_kernel  the action values of n observations under one sample, or the mean network.
 //   nz_target_kernel   pass 1 alone; both heads formed once per launch.
 //   nz_grad_kernel     ns_grad_kernel with both heads formed once per launch; eps_t waits in LDS (a word per thread, read by its writer: no barrier) for the slab
 //                      store, where slab[SIGMA + t] = gh * eps_t.
 //   nz_reduce_kernel   fixed-order slab sum (+ Adam) over 11,274 elements.
 //   nz_noise_kernel    one sample written out as the kernels form it (the tests' view of the draw).
-// pd_smem, pd_torso_rows, pd_values, pd_argmax, pd_target_value and the walk's hand-off are COPIES of mi_nstep.hip's / mi_pdd.hip's: those libraries' sources are
-// pinned by their ids.  nz_normal is a copy of mi_sac.hip's keyed_normal expression with the stream as an argument (that file cannot be included).
+// The dueling head in LDS, the three-evaluation torso rows, the action values, the gradient row, the slab epilogue and the walk's hand-off are mi_dueling.h's,
+// shared with mi_pdd.hip and mi_nstep.hip; this library forms the head it puts there and adds the sigma half of the slab.  nz_normal is a copy of mi_sac.hip's
+// keyed_normal expression with the stream as an argument (that file cannot be included).
 // All arithmetic on the VALU in fp32; no floating-point atomics, no inline assembly, no device-wide hand-off inside a launch.
 // Uses mi_common.h read-only for the device helpers; none of its host-side macros (they call into libmirl.so).
 #include "mi_common.h"
 #include "mi_ring.h"
 #include "mi_torso.h"
 #include "mi_nwalk.h"
+#include "mi_dueling.h"
 
 #include "../../include/mi_noisy.h"
 
-#define PD_H1 MI_NZ_H1
-#define PD_H2 MI_NZ_H2
-#define PD_HEAD MI_NZ_WV                      // the head's first mean
-#define PD_SIGMA MI_NZ_SIGMA                  // the head's first sigma
-#define PD_NHEAD MI_NZ_NHEAD                  // 255: Wv[84] bv Wa[2][84] ba[2]
-#define PD_WV 0                               // offsets inside the head
-#define PD_BV (MI_NZ_BV - MI_NZ_WV)
-#define PD_WA (MI_NZ_WA - MI_NZ_WV)
-#define PD_BA (MI_NZ_BA - MI_NZ_WV)
+#define PD_SIGMA MI_NZ_SIGMA                  // the head's first sigma (its first mean is DU_HEAD)
 #define PD_NP MI_NZ_NPARAMS
 #define PD_STRIDE MI_NZ_SLAB_STRIDE
 static_assert(MI_NZ_OK == RG_OK && MI_NZ_EINVAL == RG_EINVAL && MI_NZ_EHIP == RG_EHIP && MI_NZ_MAX_STEPS_PER_CALL == RG_MAX_STEPS, "mi_ring.h returns these");
 static_assert(MI_NZ_W1 == TS_W1 && MI_NZ_B1 == TS_B1 && MI_NZ_W2 == TS_W2 && MI_NZ_B2 == TS_B2 && MI_NZ_H1 == TS_H1 && MI_NZ_H2 == TS_H2, "mi_torso.h holds this torso");
-static_assert(MI_NZ_WV == TS_B2 + TS_H2 && MI_NZ_BV == MI_NZ_WV + PD_H2 && MI_NZ_WA == MI_NZ_BV + 1 && MI_NZ_BA == MI_NZ_WA + 2 * PD_H2 && PD_SIGMA == MI_NZ_BA + 2, "the head");
-static_assert(PD_NHEAD == PD_SIGMA - PD_HEAD && PD_NP == PD_SIGMA + PD_NHEAD && PD_NHEAD <= 256, "one head element per thread, mu and then sigma");
-static_assert(MI_NZ_NXI == 2 * PD_H2 + 3 && MI_NZ_NXI <= 256, "84 + 1 value factors, 84 + 2 advantage factors; b * 256 + c keys them");
+static_assert(MI_NZ_WV == DU_HEAD + DU_WV && MI_NZ_BV == DU_HEAD + DU_BV && MI_NZ_WA == DU_HEAD + DU_WA && MI_NZ_BA == DU_HEAD + DU_BA && MI_NZ_NHEAD == DU_NHEAD,
+              "mi_dueling.h holds this head");
+static_assert(PD_SIGMA == DU_HEAD + DU_NHEAD && PD_NP == PD_SIGMA + DU_NHEAD, "mu and then sigma");
+static_assert(MI_NZ_NXI == 2 * TS_H2 + 3 && MI_NZ_NXI <= 256, "84 + 1 value factors, 84 + 2 advantage factors; b * 256 + c keys them");
 static_assert(PD_STRIDE % 4 == 0 && PD_STRIDE > PD_NP, "float4 stores");
 static_assert(MI_NZ_MAX_N == NW_MAX_N, "mi_nwalk.h walks this far");
 static_assert(MI_NZ_STREAM_ACT < 16 && MI_NZ_STREAM_LEARN < 16, "the stream tag has 4 bits");
@@ -75,37 +70,25 @@ __device__ __forceinline__ float nz_xi(const nz_key& k, int c) {
 // eps of head element t < 255: the output factor, times the input factor for a weight
 __device__ __forceinline__ float nz_eps(const nz_key& k, int t) {
     int co, ci;   // the factors' indices; ci < 0: a bias
-    if (t < PD_BV) { co = PD_H2; ci = t; }
-    else if (t == PD_BV) { co = PD_H2; ci = -1; }
-    else if (t < PD_BA) { const int rel = t - PD_WA, j = rel / PD_H2; co = 2 * PD_H2 + 1 + j; ci = PD_H2 + 1 + (rel - j * PD_H2); }
-    else { co = 2 * PD_H2 + 1 + (t - PD_BA); ci = -1; }
+    if (t < DU_BV) { co = TS_H2; ci = t; }
+    else if (t == DU_BV) { co = TS_H2; ci = -1; }
+    else if (t < DU_BA) { const int rel = t - DU_WA, j = rel / TS_H2; co = 2 * TS_H2 + 1 + j; ci = TS_H2 + 1 + (rel - j * TS_H2); }
+    else { co = 2 * TS_H2 + 1 + (t - DU_BA); ci = -1; }
     const float xo = nz_xi(k, co);
     return ci >= 0 ? xo * nz_xi(k, ci) : xo;
 }
 
-// ---- the network as one workgroup holds it (mi_pdd.hip's, copied) -----------------------------------------
-enum { PD_ROW = 0, PD_NEXT = 1, PD_TGT = 2, PD_EVALS = 3 };
-enum { PD_ONLINE = 0, PD_TARGET = 1 };
-struct pd_smem {
-    float h1[PD_EVALS][PD_H1];
-    float p2[PD_EVALS][3][PD_H2];       // layer 2's partial chains
-    float h2[PD_EVALS][PD_H2];
-    float hd[2][256];                   // [network] (acting: two alternating copies of the online head): the EFFECTIVE head in parameter order; element 255 is never touched
-    float dz2[PD_H2];
-    float ph[2][PD_H1];                 // the backward's partial chains of dh1
+// ---- the head as this library holds it -------------------------------------------------------------------
+// mi_dueling.h's state, where sm.hd is the EFFECTIVE head (acting: two alternating copies of the online head), and the gradient launch's eps
+struct nz_smem : du_smem {
     float eps[256];                     // the gradient launch: eps of the online head, a word per thread, read only by its writer
 };
 
-// the mean head of the parameters P into sm.hd[net], element by element (it starts at an odd offset); the caller's next barrier (every torso evaluation has
-// three) publishes it
-__device__ __forceinline__ void pd_load_head(pd_smem& sm, int net, const float* __restrict__ P, int t) {
-    if (t < PD_NHEAD) sm.hd[net][t] = P[PD_HEAD + t];
-}
 // the effective head mu + sigma * eps of the parameters P under sample k into sm.hd[net] (noisy == 0: the mean head, no draw); returns eps_t (0 when off or t == 255)
-__device__ __forceinline__ float nz_form_head(pd_smem& sm, int net, const float* __restrict__ P, const nz_key& k, int noisy, int t) {
+__device__ __forceinline__ float nz_form_head(nz_smem& sm, int net, const float* __restrict__ P, const nz_key& k, int noisy, int t) {
     float eps = 0.0f;
-    if (t < PD_NHEAD) {
-        const float mu = P[PD_HEAD + t];
+    if (t < DU_NHEAD) {
+        const float mu = P[DU_HEAD + t];
         if (noisy) {
             eps = nz_eps(k, t);
             sm.hd[net][t] = mu + P[PD_SIGMA + t] * eps;   // -ffp-contract=off: a product, then a sum
@@ -116,58 +99,13 @@ __device__ __forceinline__ float nz_form_head(pd_smem& sm, int net, const float*
     return eps;
 }
 
-template <bool ROW, bool NEXT>
-__device__ __forceinline__ void pd_torso_rows(const ts_torso& on, const ts_torso& tg, const float4 xi, const float4 xn, pd_smem& sm, int t) {
-    if (t < PD_H1) {
-        if (ROW) sm.h1[PD_ROW][t] = ts_h1(on, xi);
-        if (NEXT) { sm.h1[PD_NEXT][t] = ts_h1(on, xn); sm.h1[PD_TGT][t] = ts_h1(tg, xn); }
-    }
-    __syncthreads();
-    if (t < 3 * PD_H2) {
-        const int c = t / PD_H2, o = t - c * PD_H2;
-        if (ROW) sm.p2[PD_ROW][c][o] = ts_p2(on, &sm.h1[PD_ROW][TS_W2C * c]);
-        if (NEXT) { sm.p2[PD_NEXT][c][o] = ts_p2(on, &sm.h1[PD_NEXT][TS_W2C * c]); sm.p2[PD_TGT][c][o] = ts_p2(tg, &sm.h1[PD_TGT][TS_W2C * c]); }
-    }
-    __syncthreads();
-    if (t < PD_H2) {
-        if (ROW) sm.h2[PD_ROW][t] = ts_h2(sm.p2[PD_ROW], t);
-        if (NEXT) { sm.h2[PD_NEXT][t] = ts_h2(sm.p2[PD_NEXT], t); sm.h2[PD_TGT][t] = ts_h2(sm.p2[PD_TGT], t); }
-    }
-    __syncthreads();
-}
-
-// THE two action values (mi_pdd.h) of evaluation `ev` through the head sm.hd[net], in every thread
-__device__ __forceinline__ void pd_values(const pd_smem& sm, int ev, int net, float& q0, float& q1) {
-    const float* const hd = sm.hd[net];
-    float v = hd[PD_BV], a0 = hd[PD_BA], a1 = hd[PD_BA + 1];
-#pragma unroll
-    for (int k = 0; k < PD_H2; ++k) {
-        const float h = sm.h2[ev][k];
-        v = __builtin_fmaf(hd[PD_WV + k], h, v);
-        a0 = __builtin_fmaf(hd[PD_WA + k], h, a0);
-        a1 = __builtin_fmaf(hd[PD_WA + PD_H2 + k], h, a1);
-    }
-    const float m = (a0 + a1) * 0.5f;
-    q0 = v + (a0 - m);
-    q1 = v + (a1 - m);
-}
-__device__ __forceinline__ int pd_argmax(float q0, float q1) { return q1 > q0 ? 1 : 0; }   // torch.argmax: the first index on a tie
-
-__device__ __forceinline__ void pd_target_value(const pd_smem& sm, float r, float lg, int& a_star, float& tgt) {
-    float q0, q1, t0, t1;
-    pd_values(sm, PD_NEXT, PD_ONLINE, q0, q1);
-    pd_values(sm, PD_TGT, PD_TARGET, t0, t1);
-    a_star = pd_argmax(q0, q1);
-    tgt = r + lg * (a_star ? t1 : t0);   // -ffp-contract=off: a product, then a sum
-}
-
 // =====================================================================================================
 // the sample, written out
 // =====================================================================================================
 __global__ void __launch_bounds__(256) nz_noise_kernel(nz_key k, float* __restrict__ xi_out, float* __restrict__ eps_out) {
     const int t = threadIdx.x;
     if (t < MI_NZ_NXI) xi_out[t] = nz_xi(k, t);
-    if (t < PD_NHEAD) eps_out[t] = nz_eps(k, t);
+    if (t < DU_NHEAD) eps_out[t] = nz_eps(k, t);
 }
 
 // =====================================================================================================
@@ -175,18 +113,18 @@ __global__ void __launch_bounds__(256) nz_noise_kernel(nz_key k, float* __restri
 // =====================================================================================================
 __global__ void __launch_bounds__(256) nz_forward_kernel(const float* __restrict__ params, const float* __restrict__ obs, int n, nz_key key, int noisy,
                                                          float* __restrict__ q) {
-    __shared__ pd_smem sm;
+    __shared__ nz_smem sm;
     const int t = threadIdx.x;
     ts_torso w;
     ts_load(w, params, t);
-    nz_form_head(sm, PD_ONLINE, params, key, noisy, t);
+    nz_form_head(sm, DU_ONLINE, params, key, noisy, t);
     for (int row = blockIdx.x; row < n; row += gridDim.x) {
         const float4 x = reinterpret_cast<const float4*>(obs)[row];
-        pd_torso_rows<true, false>(w, w, x, x, sm, t);
+        du_torso_rows<true, false>(w, w, x, x, sm, t);
         float q0, q1;
-        pd_values(sm, PD_ROW, PD_ONLINE, q0, q1);
+        du_values(sm, DU_ROW, DU_ONLINE, q0, q1);
         if (t == 0) { q[2 * (size_t)row] = q0; q[2 * (size_t)row + 1] = q1; }
-        // no barrier here: sm.h2 is next written behind two barriers of the next pd_torso_rows, which no wave passes before all have read it
+        // no barrier here: sm.h2 is next written behind two barriers of the next du_torso_rows, which no wave passes before all have read it
     }
 }
 
@@ -197,34 +135,34 @@ __global__ void __launch_bounds__(256) nz_forward_kernel(const float* __restrict
 template <bool NOISY>
 struct nz_policy {
     const ts_torso& w;
-    pd_smem& sm;
+    nz_smem& sm;
     int t;
     uint64_t seed;
     float mu, sigma;
     int cur;   // the copy of sm.hd the last greedy step read (workgroup-uniform); NOISY false: always 0, the mean head loaded at the kernel's start
     __device__ __forceinline__ int greedy(const float4& x, int, int, uint64_t env_id, uint64_t ctr) {
         if (NOISY) {
-            // the other copy: its last readers (the greedy step before the previous one) left pd_values before any wave passed the previous step's three barriers
+            // the other copy: its last readers (the greedy step before the previous one) left du_values before any wave passed the previous step's three barriers
             cur ^= 1;
-            if (t < PD_NHEAD) sm.hd[cur][t] = mu + sigma * nz_eps(nz_key{seed, env_id, ctr, MI_NZ_STREAM_ACT}, t);
+            if (t < DU_NHEAD) sm.hd[cur][t] = mu + sigma * nz_eps(nz_key{seed, env_id, ctr, MI_NZ_STREAM_ACT}, t);
         }
-        pd_torso_rows<true, false>(w, w, x, x, sm, t);   // its barriers publish the head
+        du_torso_rows<true, false>(w, w, x, x, sm, t);   // its barriers publish the head
         float q0, q1;
-        pd_values(sm, PD_ROW, NOISY ? cur : 0, q0, q1);
-        return pd_argmax(q0, q1);
+        du_values(sm, DU_ROW, NOISY ? cur : 0, q0, q1);
+        return du_argmax(q0, q1);
     }
 };
 
 // NOISY false is pdd_act_kernel: the draw's code and registers are not in that instantiation at all
 template <bool FORCED, bool NOISY>
 __global__ void __launch_bounds__(256) nz_act_kernel(mi_env e, mi_nz_ring_t ring, mi_nz_act_t a_, rg_eps_tab eps) {
-    __shared__ pd_smem sm;
+    __shared__ nz_smem sm;
     const int t = threadIdx.x;
     ts_torso w;
     ts_load(w, a_.params, t);
-    pd_load_head(sm, 0, a_.params, t);
-    const float sigma = NOISY && t < PD_NHEAD ? a_.params[PD_SIGMA + t] : 0.0f;
-    const float mu = NOISY && t < PD_NHEAD ? a_.params[PD_HEAD + t] : 0.0f;
+    du_load_head(sm, 0, a_.params, t);
+    const float sigma = NOISY && t < DU_NHEAD ? a_.params[PD_SIGMA + t] : 0.0f;
+    const float mu = NOISY && t < DU_NHEAD ? a_.params[DU_HEAD + t] : 0.0f;
     __syncthreads();
     nz_policy<NOISY> policy{w, sm, t, e.seed, mu, sigma, 0};
     const rg_act_args a{a_.obs_cur, a_.forced_actions, a_.forced_resets, a_.episodes, a_.episode_stats, a_.global_step, a_.learning_starts, a_.n_steps, a_.max_ep};
@@ -232,112 +170,62 @@ __global__ void __launch_bounds__(256) nz_act_kernel(mi_env e, mi_nz_ring_t ring
 }
 
 // =====================================================================================================
-// targets, loss, gradient (mi_nstep.hip's, copied, under the two learning samples)
+// targets, loss, gradient (the rows of mi_nstep.hip, under the two learning samples)
 // =====================================================================================================
-struct ns_walk_lds { float R, lg; int m; int pad; };
-__device__ __forceinline__ float4 ns_walk_row(const mi_nz_ring_t& ring, const mi_nz_batch_t& bt, long long i, long long total, ns_walk_lds& out, int t) {
-    float4 xn = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
-    if (t < 128) {
-        const nw_walk_t w = nw_walk(ring, i, total, bt.n_step, bt.head_slot, bt.gamma);
-        xn = reinterpret_cast<const float4*>(ring.observations)[w.at];
-        if (t == 0) { out.R = w.R; out.lg = w.lg; out.m = w.m; }
-    }
-    return xn;
-}
-
 __global__ void __launch_bounds__(256) nz_target_kernel(mi_nz_ring_t ring, mi_nz_batch_t bt) {
-    __shared__ pd_smem sm;
-    __shared__ ns_walk_lds wk[2];
+    __shared__ nz_smem sm;
+    __shared__ du_walk_lds wk[2];
     int par = 0;   // which of wk this row uses
     const int t = threadIdx.x;
     const long long total = ring.slots * (long long)ring.n_envs;
-    nz_form_head(sm, PD_ONLINE, bt.params, nz_key{bt.sample_seed, bt.sample_update, 0, MI_NZ_STREAM_LEARN}, bt.noisy, t);
-    nz_form_head(sm, PD_TARGET, bt.target_params, nz_key{bt.sample_seed, bt.sample_update, 1, MI_NZ_STREAM_LEARN}, bt.noisy, t);
+    nz_form_head(sm, DU_ONLINE, bt.params, nz_key{bt.sample_seed, bt.sample_update, 0, MI_NZ_STREAM_LEARN}, bt.noisy, t);
+    nz_form_head(sm, DU_TARGET, bt.target_params, nz_key{bt.sample_seed, bt.sample_update, 1, MI_NZ_STREAM_LEARN}, bt.noisy, t);
     ts_torso on, tg;
     ts_load(on, bt.params, t);
     ts_load(tg, bt.target_params, t);
     for (int b = blockIdx.x; b < bt.batch; b += gridDim.x) {
         long long i = bt.idx[b];
         i = i < 0 ? 0 : (i >= total ? total - 1 : i);   // a bad index reads a valid row, never past the ring
-        const float4 xn = ns_walk_row(ring, bt, i, total, wk[par], t);
-        pd_torso_rows<false, true>(on, tg, xn, xn, sm, t);
+        const float4 xn = du_walk_row(ring, bt, i, total, wk[par], t);
+        du_torso_rows<false, true>(on, tg, xn, xn, sm, t);
         int a_star; float tgt;
-        pd_target_value(sm, wk[par].R, wk[par].lg, a_star, tgt);
+        du_target_value(sm, wk[par].R, wk[par].lg, a_star, tgt);
         if (t == 0) { bt.next_actions[b] = a_star; bt.target[b] = tgt; bt.horizon[b] = wk[par].m; }
         par ^= 1;
     }
 }
 
 __global__ void __launch_bounds__(256) nz_grad_kernel(mi_nz_ring_t ring, mi_nz_batch_t bt, float* __restrict__ slabs) {
-    __shared__ pd_smem sm;
-    __shared__ ns_walk_lds wk[2];
+    __shared__ nz_smem sm;
+    __shared__ du_walk_lds wk[2];
     int par = 0;   // which of wk this row uses
     const int t = threadIdx.x;
     const long long total = ring.slots * (long long)ring.n_envs;
     // the two heads, once per launch, ahead of the torsos' loads (the draw's temporaries are dead before the 2 x 46 resident floats arrive); eps_t of the online
     // head waits in this thread's LDS word for the slab store
-    sm.eps[t] = nz_form_head(sm, PD_ONLINE, bt.params, nz_key{bt.sample_seed, bt.sample_update, 0, MI_NZ_STREAM_LEARN}, bt.noisy, t);
-    nz_form_head(sm, PD_TARGET, bt.target_params, nz_key{bt.sample_seed, bt.sample_update, 1, MI_NZ_STREAM_LEARN}, bt.noisy, t);
+    sm.eps[t] = nz_form_head(sm, DU_ONLINE, bt.params, nz_key{bt.sample_seed, bt.sample_update, 0, MI_NZ_STREAM_LEARN}, bt.noisy, t);
+    nz_form_head(sm, DU_TARGET, bt.target_params, nz_key{bt.sample_seed, bt.sample_update, 1, MI_NZ_STREAM_LEARN}, bt.noisy, t);
     ts_torso on, tg;   // the online network is loaded once and serves both online passes
     ts_load(on, bt.params, t);
     ts_load(tg, bt.target_params, t);
-    float gh = 0.0f, loss = 0.0f;   // gh: the gradient of effective head element t (t < 255)
-    ts_grads g;
-    ts_zero(g);
+    du_grads G;   // G.gh: the gradient of EFFECTIVE head element t; the torso's backward reads the effective head
+    du_zero(G);
     const float inv = 1.0f / (float)bt.batch;
-    const float* __restrict__ P = bt.params;
-    // what head element t is: a value weight, the value bias, an advantage weight of action hact, or an advantage bias of action hact; hk its h2 index
-    const int hrel = t - PD_WA;
-    const bool is_wv = t < PD_BV, is_bv = t == PD_BV, is_wa = t >= PD_WA && t < PD_BA, is_ba = t >= PD_BA && t < PD_NHEAD;
-    const int hact = is_wa ? hrel / PD_H2 : t - PD_BA;
-    const int hk = is_wv ? t : (is_wa ? hrel - hact * PD_H2 : 0);
+    const du_elem he = du_classify(t);
     for (int b = blockIdx.x; b < bt.batch; b += gridDim.x) {
         const long long i = rg_row_index(bt.sample_seed, bt.sample_update, bt.sample_upper, bt.idx, b, total, t == 0);
-        const float4 xn = ns_walk_row(ring, bt, i, total, wk[par], t);
+        const float4 xn = du_walk_row(ring, bt, i, total, wk[par], t);
         const float4 xi = reinterpret_cast<const float4*>(ring.observations)[i];
         const int a = ring.actions[i] != 0 ? 1 : 0;
         const float wb = bt.weights ? bt.weights[b] : 1.0f;
-        pd_torso_rows<true, true>(on, tg, xi, xn, sm, t);
-        // ---- pass 1, obs[s_m]: the online argmax, the target network's value of it ----
-        int a_star; float tgt;
-        pd_target_value(sm, wk[par].R, wk[par].lg, a_star, tgt);
-        // ---- pass 2, obs[i]: the stored action's online value, |td|, the weighted loss, the backward into register accumulators ----
-        float c0, c1;
-        pd_values(sm, PD_ROW, PD_ONLINE, c0, c1);
-        const float cur = a ? c1 : c0;
-        const float td = tgt - cur;
-        const float d = -(((2.0f * td) * wb) * inv);
-        const float e = 0.5f * d;
-        if (t == 0) {
+        du_grad_row(G, sm, on, tg, xi, xn, a, wk[par].R, wk[par].lg, wb, inv, he, bt.params, t, [&](int a_star, float tgt, float cur, float td) {
             bt.next_actions[b] = a_star; bt.target[b] = tgt; bt.current[b] = cur; bt.td_abs[b] = fabsf(td); bt.horizon[b] = wk[par].m;
-            loss += wb * (td * td);
-        }
-        // the head: q_a = v + 0.5 A_a - 0.5 A_{1 - a}
-        {
-            const float h = sm.h2[PD_ROW][hk];
-            const float es = hact == a ? e : -e;
-            if (is_wv) gh = __builtin_fmaf(d, h, gh);
-            else if (is_wa) gh = __builtin_fmaf(es, h, gh);
-            else if (is_bv) gh += d;
-            else if (is_ba) gh += es;
-        }
-        if (t < PD_H2) {   // the torso's backward reads the effective head
-            const float* const hd = sm.hd[PD_ONLINE];
-            const float wa_a = hd[PD_WA + a * PD_H2 + t], wa_o = hd[PD_WA + (1 - a) * PD_H2 + t];
-            sm.dz2[t] = sm.h2[PD_ROW][t] > 0.0f ? (d * hd[PD_WV + t]) + (e * (wa_a - wa_o)) : 0.0f;
-        }
-        __syncthreads();
-        ts_backward(g, sm.h1[PD_ROW], sm.dz2, sm.ph, xi, P, t);   // sm.h1 / sm.ph / sm.dz2 are then the next row's
+        });
         par ^= 1;
     }
-    // ---- the workgroup's slab ----
     float* const slab = slabs + (size_t)blockIdx.x * PD_STRIDE;
-    if (t < PD_NHEAD) {
-        slab[PD_HEAD + t] = gh;
-        slab[PD_SIGMA + t] = bt.noisy ? gh * sm.eps[t] : 0.0f;   // one product; off: exact zeros
-    }
-    ts_store(g, slab, t);
-    if (t == 0) slab[PD_NP] = loss;
+    if (t < DU_NHEAD) slab[PD_SIGMA + t] = bt.noisy ? G.gh * sm.eps[t] : 0.0f;   // one product; off: exact zeros
+    du_store(G, slab, PD_NP, t);
 }
 
 __global__ void __launch_bounds__(32 * RG_RED_GROUPS) nz_reduce_kernel(const float* __restrict__ slabs, int n_slabs, float inv, float* __restrict__ grads,
@@ -367,13 +255,9 @@ extern "C" int mi_nz_forward(const float* params, const float* obs, int n, const
 
 extern "C" int mi_nz_act_steps(void* handle, const mi_nz_ring_t* ring, const mi_nz_act_t* a, void* stream) {
     const mi_env* e = (const mi_env*)handle;
-    RG_CHECK_ARG(e != nullptr && a != nullptr, "NULL pointer");
-    RG_CHECK_ARG(a->global_step >= 0 && a->total_timesteps > 0 && a->exploration_fraction > 0.0, "global_step < 0, total_timesteps <= 0 or exploration_fraction <= 0");
-    RG_CHECK_ARG(a->learning_starts >= 0, "learning_starts < 0");
     hipStream_t s = (hipStream_t)stream;
     rg_eps_tab tab;
-    rg_eps_fill(tab, a->global_step, (a->end_e - a->start_e) / (a->exploration_fraction * (double)a->total_timesteps), a->start_e, a->end_e);
-    for (int k = 0; k < RG_MAX_STEPS; ++k) tab.v[k] = (double)(float)tab.v[k];   // DQN compares the draw with epsilon as an f32 (mi_pdd_act_steps)
+    DU_ACT_EPSILON(e, a, tab);
     int grid;
     const int rc = rg_act_prelude(e, ring, a->params, a->obs_cur, a->n_steps, a->max_ep, a->episodes, a->episode_stats, s, grid);
     if (rc != MI_NZ_OK) return rc;
@@ -389,21 +273,11 @@ extern "C" int mi_nz_act_steps(void* handle, const mi_nz_ring_t* ring, const mi_
     return MI_NZ_OK;
 }
 
-// the members only the walk needs (a macro: the error text names the entry point that was called); mi_nstep.hip's three checks
-#define NZ_CHECK_WALK(ring, b)                                                                                                                          \
-    do {                                                                                                                                                \
-        RG_CHECK_ARG((b)->horizon != nullptr, "horizon is NULL");                                                                                       \
-        RG_CHECK_ARG((b)->n_step >= 1 && (b)->n_step <= MI_NZ_MAX_N && (int64_t)(b)->n_step < (ring)->slots, "n_step must be in [1, 16] and below slots"); \
-        RG_CHECK_ARG((b)->head_slot >= 0 && (b)->head_slot < (ring)->slots, "head_slot outside [0, slots)");                                            \
-    } while (0)
-
 extern "C" int mi_nz_target(const mi_nz_ring_t* ring, const mi_nz_batch_t* b, void* stream) {
     const int rc = rg_check_ring(ring);
     if (rc != MI_NZ_OK) return rc;
-    RG_CHECK_ARG(b != nullptr, "batch is NULL");
-    RG_CHECK_ARG(b->params && b->target_params && b->idx && b->next_actions && b->target && b->batch > 0, "bad arguments");
-    RG_CHECK_ARG(rg_aligned(b->params) && rg_aligned(b->target_params), "params and target_params must be 16-byte aligned");
-    NZ_CHECK_WALK(ring, b);
+    DU_CHECK_TARGET(b);
+    DU_CHECK_WALK(ring, b);
     nz_target_kernel<<<b->batch < 1024 ? b->batch : 1024, 256, 0, (hipStream_t)stream>>>(*ring, *b);
     RG_HIP(hipGetLastError());
     return MI_NZ_OK;
@@ -413,7 +287,7 @@ extern "C" int mi_nz_target(const mi_nz_ring_t* ring, const mi_nz_batch_t* b, vo
 static int nz_grad(const mi_nz_ring_t* ring, const mi_nz_batch_t* b, const mi_nz_adam_t* opt, bool update, hipStream_t s) {
     int rc = rg_check_batch(ring, b, INT_MAX, "batch <= 0", [](const mi_nz_batch_t& bt) { return bt.current && bt.target && bt.td_abs; });
     if (rc != RG_OK) return rc;
-    NZ_CHECK_WALK(ring, b);
+    DU_CHECK_WALK(ring, b);
     if (update) rc = rg_check_opt(opt);
     if (rc != RG_OK) return rc;
     return rg_launch_grad<PD_NP>(nz_grad_kernel, nz_reduce_kernel, ring, b, nz_slabs(b->batch), 1.0f / (float)b->batch, update ? opt : nullptr, s);

@@ -21,9 +21,9 @@ OLDER = (
     ("_native_iqn", ["mi_iqn.hip", "mi_common.h", "mi_ring.h", INC + "mi_iqn.h", INC + "mi_rl.h"], "e35a43ebf95c"),
     ("_native_qr", ["mi_qr.hip", "mi_common.h", "mi_ring.h", "mi_torso.h", INC + "mi_qr.h", INC + "mi_rl.h"], "8100cd09ac96"),
     ("_native_ddqn", ["mi_ddqn.hip", "mi_common.h", "mi_ring.h", "mi_torso.h", INC + "mi_ddqn.h", INC + "mi_rl.h"], "45a0ddad7ca6"),
-    ("_native_pdd", ["mi_pdd.hip", "mi_common.h", "mi_ring.h", "mi_torso.h", INC + "mi_pdd.h", INC + "mi_rl.h"], "0b7d86964c81"),
-    ("_native_ns", ["mi_nstep.hip", "mi_common.h", "mi_ring.h", "mi_torso.h", "mi_nwalk.h", INC + "mi_nstep.h", INC + "mi_rl.h"], "908cc9f02915"),
-    ("_native_nz", ["mi_noisy.hip", "mi_common.h", "mi_ring.h", "mi_torso.h", "mi_nwalk.h", INC + "mi_noisy.h", INC + "mi_rl.h"], "4c1c4febd2ce"),
+    ("_native_pdd", ["mi_pdd.hip", "mi_common.h", "mi_ring.h", "mi_torso.h", "mi_dueling.h", INC + "mi_pdd.h", INC + "mi_rl.h"], "65d24581dff3"),
+    ("_native_ns", ["mi_nstep.hip", "mi_common.h", "mi_ring.h", "mi_torso.h", "mi_nwalk.h", "mi_dueling.h", INC + "mi_nstep.h", INC + "mi_rl.h"], "ffb74331a9c8"),
+    ("_native_nz", ["mi_noisy.hip", "mi_common.h", "mi_ring.h", "mi_torso.h", "mi_nwalk.h", "mi_dueling.h", INC + "mi_noisy.h", INC + "mi_rl.h"], "74e65f9c5f40"),
     ("_native_rb", ["mi_rainbow.hip", "mi_common.h", "mi_ring.h", "mi_torso.h", "mi_nwalk.h", INC + "mi_rainbow.h", INC + "mi_rl.h"], "47a9b95b193c"),
 )
 LIBMIRL_ID = "6106efad96ba"

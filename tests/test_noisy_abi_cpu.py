@@ -12,7 +12,7 @@ import pytest
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 CSRC = os.path.join(ROOT, "deep_rl_amd", "csrc")
-NZ_ALLSRC = ["mi_noisy.hip", "mi_common.h", "mi_ring.h", "mi_torso.h", "mi_nwalk.h", "../../include/mi_noisy.h", "../../include/mi_rl.h"]
+NZ_ALLSRC = ["mi_noisy.hip", "mi_common.h", "mi_ring.h", "mi_torso.h", "mi_nwalk.h", "mi_dueling.h", "../../include/mi_noisy.h", "../../include/mi_rl.h"]
 ENTRY = ("version", "last_error", "source_id", "workspace_bytes", "noise", "forward", "act_steps", "target", "grad", "update")
 
 
@@ -56,7 +56,8 @@ def test_header_symbols_all_exported_and_bound(K):
         assert inc in src
     for call in ("rg_check_batch(", "rg_check_opt(", "rg_launch_grad<", "rg_check_ring(", "rg_act_prelude(", "rg_act_loop<", "rg_reduce<PD_NP, PD_STRIDE>"):
         assert call in src, call
-    code = re.sub(r"//.*", "", src)
+    assert '#include "mi_dueling.h"' in src and "template <bool ROW, bool NEXT>" not in src      # the head and the batch row are the shared header's, not a copy
+    code = re.sub(r"//.*", "", src + open(os.path.join(CSRC, "mi_dueling.h")).read())
     assert "asm" not in code and "atomicAdd(" not in code and "mi_sac" not in code
     # the streams 13 and 14 are new: no other source uses them as a Philox stream tag
     assert "MI_NZ_STREAM_ACT" in src and "MI_NZ_STREAM_LEARN" in src

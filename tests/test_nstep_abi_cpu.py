@@ -12,7 +12,7 @@ import pytest
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 CSRC = os.path.join(ROOT, "deep_rl_amd", "csrc")
-NS_ALLSRC = ["mi_nstep.hip", "mi_common.h", "mi_ring.h", "mi_torso.h", "mi_nwalk.h", "../../include/mi_nstep.h", "../../include/mi_rl.h"]
+NS_ALLSRC = ["mi_nstep.hip", "mi_common.h", "mi_ring.h", "mi_torso.h", "mi_nwalk.h", "mi_dueling.h", "../../include/mi_nstep.h", "../../include/mi_rl.h"]
 
 
 @pytest.fixture(scope="module")
@@ -53,8 +53,9 @@ def test_header_symbols_all_exported_and_bound(K):
     walk = open(os.path.join(CSRC, "mi_nwalk.h")).read()
     assert "static_assert(MI_NS_W1 == TS_W1 && MI_NS_B1 == TS_B1 && MI_NS_W2 == TS_W2 && MI_NS_B2 == TS_B2" in src and "static_assert(MI_NS_MAX_N == NW_MAX_N" in src
     assert '#include "mi_nwalk.h"' in src and "rg_check_batch(" in src and "rg_check_opt(" in src and "rg_launch_grad<" in src and "rg_check_ring(" in src
-    for text in (src, walk):
+    for text in (src, walk, open(os.path.join(CSRC, "mi_dueling.h")).read()):
         assert "asm" not in text and "atomicAdd(" not in text
+    assert '#include "mi_dueling.h"' in src and "template <bool ROW, bool NEXT>" not in src      # the head and the batch row are the shared header's, not a copy
     assert "__syncthreads" not in walk and "__shared__" not in walk and "truncation" in walk and "truncation" in open(os.path.join(ROOT, "include", "mi_nstep.h")).read()
 
 

@@ -11,7 +11,7 @@ import pytest
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 CSRC = os.path.join(ROOT, "deep_rl_amd", "csrc")
-PDD_ALLSRC = ["mi_pdd.hip", "mi_common.h", "mi_ring.h", "mi_torso.h", "../../include/mi_pdd.h", "../../include/mi_rl.h"]
+PDD_ALLSRC = ["mi_pdd.hip", "mi_common.h", "mi_ring.h", "mi_torso.h", "mi_dueling.h", "../../include/mi_pdd.h", "../../include/mi_rl.h"]
 
 
 @pytest.fixture(scope="module")
@@ -52,7 +52,11 @@ def test_header_symbols_all_exported_and_bound(K):
     assert K.SLAB_STRIDE % 4 == 0 and K.SLAB_STRIDE > K.NPARAMS and K.OFF_W2 % 4 == 0
     assert hasattr(K, "Ring") and hasattr(K, "Batch") and hasattr(K, "AdamArgs") and callable(K.workspace_bytes) and callable(K.grad) and callable(K.update)
     src = open(os.path.join(CSRC, "mi_pdd.hip")).read()
-    assert "static_assert(MI_PDD_W1 == TS_W1 && MI_PDD_B1 == TS_B1 && MI_PDD_W2 == TS_W2 && MI_PDD_B2 == TS_B2" in src and "asm" not in src and "atomicAdd(" not in src
+    dueling = open(os.path.join(CSRC, "mi_dueling.h")).read()
+    assert "static_assert(MI_PDD_W1 == TS_W1 && MI_PDD_B1 == TS_B1 && MI_PDD_W2 == TS_W2 && MI_PDD_B2 == TS_B2" in src
+    for text in (src, dueling):
+        assert "asm" not in text and "atomicAdd(" not in text
+    assert '#include "mi_dueling.h"' in src and "template <bool ROW, bool NEXT>" not in src      # the head and the batch row are the shared header's, not a copy
 
 
 def _struct_fields(hdr, name):

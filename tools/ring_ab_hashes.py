@@ -1,13 +1,17 @@
 #!/usr/bin/env python3
-"""The seeded byte-for-byte sequence of a ring-replay library (C51, IQN, QR-DQN, Double DQN): what a refactor of mi_ring.h / mi_torso.h / mi_*.hip must leave unchanged.
+"""The seeded byte-for-byte sequence of a ring-replay library (C51, IQN, QR-DQN, Double DQN, prioritized dueling Double DQN and its n-step and noisy forms): what a
+refactor of mi_ring.h / mi_torso.h / mi_dueling.h / mi_*.hip must leave unchanged.
 
-    tools/ring_ab_hashes.py --algo c51|iqn|qrdqn|ddqn --envs N --slots S --batch B --out FILE
+    tools/ring_ab_hashes.py --algo c51|iqn|qrdqn|ddqn|pdd|nstep|noisy --envs N --slots S --batch B --out FILE   [--prioritized 0|1] [--n-step N] [--noisy 0|1]
 
-One process, one library (the one ``MIRL_C51_SO`` / ``MIRL_IQN_SO`` / ``MIRL_QR_SO`` / ``MIRL_DDQN_SO`` names, else the built one), no retry.  It runs
+One process, one library set (the ones ``MIRL_C51_SO`` / ``MIRL_IQN_SO`` / ``MIRL_QR_SO`` / ``MIRL_DDQN_SO`` / ``MIRL_PDD_SO`` / ``MIRL_NS_SO`` / ``MIRL_NZ_SO``
+name, else the built ones; the n-step and the noisy engine act through libmirl_pdd.so), no retry.  It runs
   1 reset   2 act(64)   3 act(7) with forced actions and resets (IQN: forced taus and taus_out too)   4 six train_step()s with deep_rl_amd.Adam
   5 sample(indices) + target() + grad() + optimizer.step   6 sync_target   7 act(64) at the epsilon floor
 and after every stage writes the sha256 of the raw bytes of every tensor: the ring, the env's fp64 state and TimeLimit counters, the carried observation,
-episode_stats, the drained episodes, batch_inds, next_actions, the target and current tensors, the taus, grads, loss, both parameter vectors and Adam's moments.
+episode_stats, the drained episodes, batch_inds, next_actions, the target and current tensors, the taus, grads, loss, both parameter vectors and Adam's moments;
+for pdd / nstep / noisy also td_abs, the n-step horizon and, prioritized, weights, priorities and max_priority.  Stage 3 is forced for every algorithm but nstep,
+which has no acting kernel of its own.  ``--noisy 0`` runs the mean network under the epsilon schedule, ``--noisy 1`` the noise with epsilon 0.
 FILE holds nothing but the stages (no library id, no time), so two runs are compared with ``cmp``; the library's id goes to stdout.
 The schedule puts stage 2 on the decaying epsilon (Double DQN and IQN: its first 16 steps before learning_starts) and stage 7 on the floor.
 """
@@ -27,7 +31,7 @@ import deep_rl_amd as D  # noqa: E402
 DECAY_STEPS, LEARNING_STARTS = 70, 16   # stages 2 and 3 take steps 0 .. 70, stage 7 steps 71 .. 134
 
 
-def make(algo, n, slots, batch, seed):
+def make(algo, n, slots, batch, seed, prioritized=True, n_step=3, noisy=True):
     """-> (engine, the names of the algorithm's own tensors)"""
     dev = torch.device("cuda", 0)
     env = D.make("CartPole-v1", num_envs=n, device=dev, seed=seed)
@@ -41,6 +45,17 @@ def make(algo, n, slots, batch, seed):
         eng = D.IQNEngine(env, p, t, D.Adam(p, lr=5e-5, eps=1e-2 / batch), slots=slots, batch_size=batch, final_epsilon=0.01, epsilon_decay_steps=DECAY_STEPS,
                           learning_starts=LEARNING_STARTS, max_episodes_logged=log)
         return eng, K, ("taus", "current_action_quantiles", "target_action_quantiles")
+    if algo in ("pdd", "nstep", "noisy"):   # the dueling networks tools/bench_pdd.py, bench_nstep.py and bench_noisy.py build
+        net, engine, K, kw = {
+            "pdd": (D.DuelingQNetwork, D.PDDDQNEngine, "_native_pdd", {}),
+            "nstep": (D.DuelingQNetwork, D.NStepDQNEngine, "_native_ns", {"n_step": n_step}),
+            "noisy": (D.NoisyDuelingQNetwork, D.NoisyDQNEngine, "_native_nz", dict(n_step=n_step, noisy=noisy, **({} if noisy else {"start_e": 1.0, "end_e": 0.05}))),
+        }[algo]
+        q = net(env); t = net(env); t.load_state_dict(q.state_dict())
+        eng = engine(env, q, t, D.Adam(q, lr=2.5e-4), slots=slots, batch_size=batch, learning_starts=LEARNING_STARTS, total_timesteps=2 * DECAY_STEPS,
+                     exploration_fraction=0.5, max_episodes_logged=log, prioritized=prioritized, **kw)
+        own = ("current", "target_values", "td_abs") + (("horizon",) if hasattr(eng, "horizon") else ()) + (("weights", "priorities", "max_priority") if prioritized else ())
+        return eng, getattr(__import__("deep_rl_amd." + K), K), own
     net, engine, K, own, kw = {
         "c51": (D.C51QNetwork, D.C51Engine, "_native_c51", ("probs", "target_probs"), {}),
         "qrdqn": (D.QRQNetwork, D.QRDQNEngine, "_native_qr", ("current", "target_quantiles"), {}),
@@ -71,14 +86,17 @@ def snapshot(eng, own, extra):
 
 def main():
     ap = argparse.ArgumentParser()
-    ap.add_argument("--algo", required=True, choices=("c51", "iqn", "qrdqn", "ddqn"))
+    ap.add_argument("--algo", required=True, choices=("c51", "iqn", "qrdqn", "ddqn", "pdd", "nstep", "noisy"))
     ap.add_argument("--envs", type=int, required=True)
     ap.add_argument("--slots", type=int, required=True)
     ap.add_argument("--batch", type=int, required=True)
     ap.add_argument("--seed", type=int, default=1)
+    ap.add_argument("--prioritized", type=int, choices=(0, 1), default=1, help="pdd / nstep / noisy: prioritized (1) or uniform (0) replay")
+    ap.add_argument("--n-step", type=int, default=3, help="nstep / noisy")
+    ap.add_argument("--noisy", type=int, choices=(0, 1), default=1, help="noisy")
     ap.add_argument("--out", required=True)
     args = ap.parse_args()
-    eng, K, own = make(args.algo, args.envs, args.slots, args.batch, args.seed)
+    eng, K, own = make(args.algo, args.envs, args.slots, args.batch, args.seed, bool(args.prioritized), args.n_step, bool(args.noisy))
     print("library", K.SO_PATH, K.source_id(), flush=True)
     n, iqn = args.envs, args.algo == "iqn"
     gen = torch.Generator().manual_seed(args.seed)
@@ -95,6 +113,8 @@ def main():
     if iqn:
         forced["forced_taus"] = torch.rand((7, n, K.N_QUANT), generator=gen, dtype=torch.float32)
         forced["taus_out"] = extra["taus_out"] = torch.zeros((7, n, K.N_QUANT), dtype=torch.float32, device=eng.device)
+    if args.algo == "nstep":   # its acting is libmirl_pdd.so's: --algo pdd covers the forced launch
+        forced = {}
     eng.act(7, **forced); stage("3 act(7) forced")
     for _ in range(6):
         eng.train_step()
