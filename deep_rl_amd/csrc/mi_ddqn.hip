@@ -10,24 +10,18 @@
 //   ddqn_reduce_kernel   fixed-order slab sum (+ Adam).
 //   ddqn_target_kernel   pass 1 alone.
 //   ddqn_forward_kernel  the action values of n observations.
-// The torso's layout, loader, per-thread pieces, backward and slab store are mi_torso.h's, shared with mi_c51.hip and mi_qr.hip; the host side of acting and of the
-// gradient entry points is mi_ring.h's.  All arithmetic on the VALU in fp32 with the summation orders of the header; no floating-point atomics.
+// The torso's layout, loader, per-thread pieces, backward and slab store are mi_torso.h's, shared with mi_c51.hip and mi_qr.hip; the head, the three evaluations of
+// a row and pass 2 of a gradient row are mi_qhead.h's, shared with mi_mdqn.hip; the host side of acting and of the gradient entry points is mi_ring.h's. All arithmetic on the VALU in fp32 with the summation orders of the header; no floating-point atomics.
 // Uses mi_common.h read-only for the device helpers; none of its host-side macros (they call into libmirl.so).
 #include "mi_common.h"
 #include "mi_ring.h"
-#include "mi_torso.h"
+#include "mi_qhead.h"
 
 #include "../../include/mi_ddqn.h"
 
-#define DD_H1 MI_DDQN_H1
-#define DD_H2 MI_DDQN_H2
-#define DD_W3 MI_DDQN_W3
-#define DD_B3 MI_DDQN_B3
-#define DD_NP MI_DDQN_NPARAMS
-#define DD_STRIDE MI_DDQN_SLAB_STRIDE
 static_assert(MI_DDQN_OK == RG_OK && MI_DDQN_EINVAL == RG_EINVAL && MI_DDQN_EHIP == RG_EHIP && MI_DDQN_MAX_STEPS_PER_CALL == RG_MAX_STEPS, "mi_ring.h returns these");
 static_assert(MI_DDQN_W1 == TS_W1 && MI_DDQN_B1 == TS_B1 && MI_DDQN_W2 == TS_W2 && MI_DDQN_B2 == TS_B2 && MI_DDQN_H1 == TS_H1 && MI_DDQN_H2 == TS_H2, "mi_torso.h holds this torso");
-static_assert(DD_STRIDE % 4 == 0 && DD_STRIDE > DD_NP, "float4 stores");
+static_assert(MI_DDQN_W3 == QH_W3 && MI_DDQN_B3 == QH_B3 && MI_DDQN_NPARAMS == QH_NP && MI_DDQN_SLAB_STRIDE == QH_STRIDE, "mi_qhead.h holds this head");
 
 #ifndef MI_DDQN_SOURCE_ID
 #define MI_DDQN_SOURCE_ID "unknown"
@@ -38,80 +32,28 @@ extern "C" const char* mi_ddqn_source_id(void) { return MI_DDQN_SOURCE_ID; }
 static int dd_slabs(int batch) { return rg_slabs(batch, MI_DDQN_MAX_SLABS); }
 extern "C" size_t mi_ddqn_workspace_bytes(int batch) {
     if (batch <= 0) return 0;
-    return (size_t)dd_slabs(batch) * DD_STRIDE * sizeof(float);
+    return (size_t)dd_slabs(batch) * QH_STRIDE * sizeof(float);
 }
 
-// ---- the network as one workgroup holds it ------------------------------------------------------------
-// the evaluations a workgroup keeps side by side: ROW the online network at obs[i], NEXT the online network at obs[nx], TGT the target network at obs[nx]
-enum { DD_ROW = 0, DD_NEXT = 1, DD_TGT = 2, DD_EVALS = 3 };
-enum { DD_ONLINE = 0, DD_TARGET = 1 };
-struct dd_smem {
-    float h1[DD_EVALS][DD_H1];
-    float p2[DD_EVALS][3][DD_H2];       // layer 2's partial chains
-    float h2[DD_EVALS][DD_H2];
-    float w3[2][2][DD_H2];              // [network][action]: the heads
-    float b3[2][2];
-    float dz2[DD_H2];
-    float ph[2][DD_H1];                 // the backward's partial chains of dh1
-};
-
-// the head of the parameters P into sm.w3[net] / sm.b3[net]; the caller's next barrier (every torso evaluation has three) publishes it
-__device__ __forceinline__ void dd_load_head(dd_smem& sm, int net, const float* __restrict__ P, int t) {
-    if (t < 2 * DD_H2) sm.w3[net][t / DD_H2][t % DD_H2] = P[DD_W3 + t];
-    else if (t < 2 * DD_H2 + 2) sm.b3[net][t - 2 * DD_H2] = P[DD_B3 + t - 2 * DD_H2];
-}
-
-// layers 1 and 2: with ROW the online torso `on` at xi (-> sm.h1 / sm.h2 [DD_ROW]), with NEXT the online torso at xn (-> [DD_NEXT]) and the target torso `tg` at xn
-// (-> [DD_TGT]), all between the same three barriers; the results are valid for every thread when it returns
-template <bool ROW, bool NEXT>
-__device__ __forceinline__ void dd_torso_rows(const ts_torso& on, const ts_torso& tg, const float4 xi, const float4 xn, dd_smem& sm, int t) {
-    if (t < DD_H1) {
-        if (ROW) sm.h1[DD_ROW][t] = ts_h1(on, xi);
-        if (NEXT) { sm.h1[DD_NEXT][t] = ts_h1(on, xn); sm.h1[DD_TGT][t] = ts_h1(tg, xn); }
-    }
-    __syncthreads();
-    if (t < 3 * DD_H2) {
-        const int c = t / DD_H2, o = t - c * DD_H2;
-        if (ROW) sm.p2[DD_ROW][c][o] = ts_p2(on, &sm.h1[DD_ROW][TS_W2C * c]);
-        if (NEXT) { sm.p2[DD_NEXT][c][o] = ts_p2(on, &sm.h1[DD_NEXT][TS_W2C * c]); sm.p2[DD_TGT][c][o] = ts_p2(tg, &sm.h1[DD_TGT][TS_W2C * c]); }
-    }
-    __syncthreads();
-    if (t < DD_H2) {
-        if (ROW) sm.h2[DD_ROW][t] = ts_h2(sm.p2[DD_ROW], t);
-        if (NEXT) { sm.h2[DD_NEXT][t] = ts_h2(sm.p2[DD_NEXT], t); sm.h2[DD_TGT][t] = ts_h2(sm.p2[DD_TGT], t); }
-    }
-    __syncthreads();
-}
-
-// THE two action values (mi_ddqn.h) of evaluation `ev` through the head of network `net`, in every thread (two independent chains; the reads are workgroup-uniform
-// broadcasts)
-__device__ __forceinline__ void dd_values(const dd_smem& sm, int ev, int net, float& q0, float& q1) {
-    q0 = sm.b3[net][0]; q1 = sm.b3[net][1];
-#pragma unroll
-    for (int k = 0; k < DD_H2; ++k) {
-        const float h = sm.h2[ev][k];
-        q0 = __builtin_fmaf(sm.w3[net][0][k], h, q0);
-        q1 = __builtin_fmaf(sm.w3[net][1][k], h, q1);
-    }
-}
-__device__ __forceinline__ int dd_argmax(float q0, float q1) { return q1 > q0 ? 1 : 0; }   // torch.argmax: the first index on a tie
+// the evaluations a workgroup keeps beside QH_ROW (the online network at obs[i]): NEXT the online network at obs[nx], TGT the target network at obs[nx]
+enum { DD_NEXT = 1, DD_TGT = 2 };
 
 // =====================================================================================================
 // forward API
 // =====================================================================================================
 __global__ void __launch_bounds__(256) ddqn_forward_kernel(const float* __restrict__ params, const float* __restrict__ obs, int n, float* __restrict__ q) {
-    __shared__ dd_smem sm;
+    __shared__ qh_smem sm;
     const int t = threadIdx.x;
     ts_torso w;
     ts_load(w, params, t);
-    dd_load_head(sm, DD_ONLINE, params, t);
+    qh_load_head(sm, QH_ONLINE, params, t);
     for (int row = blockIdx.x; row < n; row += gridDim.x) {
         const float4 x = reinterpret_cast<const float4*>(obs)[row];
-        dd_torso_rows<true, false>(w, w, x, x, sm, t);
+        qh_torso_rows<true, false>(w, x, w, x, w, x, sm, t);
         float q0, q1;
-        dd_values(sm, DD_ROW, DD_ONLINE, q0, q1);
+        qh_values(sm, QH_ROW, QH_ONLINE, q0, q1);
         if (t == 0) { q[2 * (size_t)row] = q0; q[2 * (size_t)row + 1] = q1; }
-        // no barrier here: sm.h2 is next written behind two barriers of the next dd_torso_rows, which no wave passes before all have read it
+        // no barrier here: sm.h2 is next written behind two barriers of the next qh_torso_rows, which no wave passes before all have read it
     }
 }
 
@@ -121,24 +63,24 @@ __global__ void __launch_bounds__(256) ddqn_forward_kernel(const float* __restri
 // the greedy action of rg_act_loop: the online torso in `w`, its head in LDS
 struct dd_policy {
     const ts_torso& w;
-    dd_smem& sm;
+    qh_smem& sm;
     int t;
     __device__ __forceinline__ int greedy(const float4& x, int, int, uint64_t, uint64_t) {
-        dd_torso_rows<true, false>(w, w, x, x, sm, t);
+        qh_torso_rows<true, false>(w, x, w, x, w, x, sm, t);
         float q0, q1;
-        dd_values(sm, DD_ROW, DD_ONLINE, q0, q1);
-        // no barrier here: sm.h2 is next written behind two barriers of the next dd_torso_rows, which no wave passes before all have read it
-        return dd_argmax(q0, q1);
+        qh_values(sm, QH_ROW, QH_ONLINE, q0, q1);
+        // no barrier here: sm.h2 is next written behind two barriers of the next qh_torso_rows, which no wave passes before all have read it
+        return qh_argmax(q0, q1);
     }
 };
 
 template <bool FORCED>
 __global__ void __launch_bounds__(256) ddqn_act_kernel(mi_env e, mi_ddqn_ring_t ring, mi_ddqn_act_t a_, rg_eps_tab eps) {
-    __shared__ dd_smem sm;
+    __shared__ qh_smem sm;
     const int t = threadIdx.x;
     ts_torso w;
     ts_load(w, a_.params, t);
-    dd_load_head(sm, DD_ONLINE, a_.params, t);
+    qh_load_head(sm, QH_ONLINE, a_.params, t);
     __syncthreads();
     dd_policy policy{w, sm, t};
     const rg_act_args a{a_.obs_cur, a_.forced_actions, a_.forced_resets, a_.episodes, a_.episode_stats, a_.global_step, a_.learning_starts, a_.n_steps, a_.max_ep};
@@ -148,37 +90,31 @@ __global__ void __launch_bounds__(256) ddqn_act_kernel(mi_env e, mi_ddqn_ring_t 
 // =====================================================================================================
 // targets, loss, gradient
 // =====================================================================================================
-// the successor of flat ring index i: ((slot + 1) % slots) * N + env
-__device__ __forceinline__ long long dd_successor(const mi_ddqn_ring_t& ring, long long i, long long total) {
-    const long long N = ring.n_envs;
-    return i + N >= total ? i + N - total : i + N;
-}
 // pass 1 of a row whose evaluations DD_NEXT / DD_TGT are in sm: a* by the online head, the target network's value of a* (every thread holds both)
-__device__ __forceinline__ void dd_target_value(const dd_smem& sm, float r, float lg, int& a_star, float& tgt) {
+__device__ __forceinline__ void dd_target_value(const qh_smem& sm, float r, float lg, int& a_star, float& tgt) {
     float q0, q1, t0, t1;
-    dd_values(sm, DD_NEXT, DD_ONLINE, q0, q1);
-    dd_values(sm, DD_TGT, DD_TARGET, t0, t1);
-    a_star = dd_argmax(q0, q1);
+    qh_values(sm, DD_NEXT, QH_ONLINE, q0, q1);
+    qh_values(sm, DD_TGT, QH_TARGET, t0, t1);
+    a_star = qh_argmax(q0, q1);
     tgt = r + lg * (a_star ? t1 : t0);   // -ffp-contract=off: a product, then a sum
 }
 
 __global__ void __launch_bounds__(256) ddqn_target_kernel(mi_ddqn_ring_t ring, mi_ddqn_batch_t bt) {
-    __shared__ dd_smem sm;
+    __shared__ qh_smem sm;
     const int t = threadIdx.x;
     const long long total = ring.slots * (long long)ring.n_envs;
     ts_torso on, tg;
     ts_load(on, bt.params, t);
     ts_load(tg, bt.target_params, t);
-    dd_load_head(sm, DD_ONLINE, bt.params, t);
-    dd_load_head(sm, DD_TARGET, bt.target_params, t);
+    qh_load_head(sm, QH_ONLINE, bt.params, t);
+    qh_load_head(sm, QH_TARGET, bt.target_params, t);
     for (int b = blockIdx.x; b < bt.batch; b += gridDim.x) {
-        long long i = bt.idx[b];
-        i = i < 0 ? 0 : (i >= total ? total - 1 : i);   // a bad index reads a valid row, never past the ring
-        const long long nx = dd_successor(ring, i, total);
+        const long long i = qh_clamp_index(bt.idx[b], total);
+        const long long nx = qh_successor(ring, i, total);
         const float4 xn = reinterpret_cast<const float4*>(ring.observations)[nx];
         const float r = ring.rewards[nx];
         const float lg = ring.terminated[nx] ? 0.0f : bt.gamma;
-        dd_torso_rows<false, true>(on, tg, xn, xn, sm, t);
+        qh_torso_rows<false, true>(on, xn, on, xn, tg, xn, sm, t);
         int a_star; float tgt;
         dd_target_value(sm, r, lg, a_star, tgt);
         if (t == 0) { bt.next_actions[b] = a_star; bt.target[b] = tgt; }
@@ -186,63 +122,40 @@ __global__ void __launch_bounds__(256) ddqn_target_kernel(mi_ddqn_ring_t ring, m
 }
 
 __global__ void __launch_bounds__(256) ddqn_grad_kernel(mi_ddqn_ring_t ring, mi_ddqn_batch_t bt, float* __restrict__ slabs) {
-    __shared__ dd_smem sm;
+    __shared__ qh_smem sm;
     const int t = threadIdx.x;
     const long long total = ring.slots * (long long)ring.n_envs;
     ts_torso on, tg;   // the online network is loaded once and serves both online passes
     ts_load(on, bt.params, t);
     ts_load(tg, bt.target_params, t);
-    dd_load_head(sm, DD_ONLINE, bt.params, t);
-    dd_load_head(sm, DD_TARGET, bt.target_params, t);
-    float g3 = 0.0f, gb3 = 0.0f, loss = 0.0f;
-    ts_grads g;
-    ts_zero(g);
+    qh_load_head(sm, QH_ONLINE, bt.params, t);
+    qh_load_head(sm, QH_TARGET, bt.target_params, t);
+    qh_grads G;
+    qh_zero(G);
     const float inv = 1.0f / (float)bt.batch;
     const float* __restrict__ P = bt.params;
     for (int b = blockIdx.x; b < bt.batch; b += gridDim.x) {
         const long long i = rg_row_index(bt.sample_seed, bt.sample_update, bt.sample_upper, bt.idx, b, total, t == 0);
-        const long long nx = dd_successor(ring, i, total);
+        const long long nx = qh_successor(ring, i, total);
         const float4 xi = reinterpret_cast<const float4*>(ring.observations)[i];
         const float4 xn = reinterpret_cast<const float4*>(ring.observations)[nx];
         const int a = ring.actions[i] != 0 ? 1 : 0;
         const float r = ring.rewards[nx];
         const float lg = ring.terminated[nx] ? 0.0f : bt.gamma;
-        dd_torso_rows<true, true>(on, tg, xi, xn, sm, t);
+        qh_torso_rows<true, true>(on, xi, on, xn, tg, xn, sm, t);
         // ---- pass 1, obs[nx]: the online argmax, the target network's value of it ----
         int a_star; float tgt;
         dd_target_value(sm, r, lg, a_star, tgt);
         // ---- pass 2, obs[i]: the stored action's online value, the loss, the backward into register accumulators ----
-        float c0, c1;
-        dd_values(sm, DD_ROW, DD_ONLINE, c0, c1);
-        const float cur = a ? c1 : c0;
-        const float td = tgt - cur;
-        const float d = -((2.0f * td) * inv);
-        if (t == 0) {
-            bt.next_actions[b] = a_star; bt.target[b] = tgt; bt.current[b] = cur;
-            loss += td * td;
-        }
-        // layer 3: thread a' * 84 + k owns dW3[a'][k], thread 168 + a' db3[a']; the other action's row is not touched
-        if (t < 2 * DD_H2) {
-            if (t / DD_H2 == a) g3 = __builtin_fmaf(d, sm.h2[DD_ROW][t % DD_H2], g3);
-        } else if (t - 2 * DD_H2 == a) {
-            gb3 += d;
-        }
-        if (t < DD_H2) sm.dz2[t] = sm.h2[DD_ROW][t] > 0.0f ? d * sm.w3[DD_ONLINE][a][t] : 0.0f;
-        __syncthreads();
-        ts_backward(g, sm.h1[DD_ROW], sm.dz2, sm.ph, xi, P, t);   // sm.h1 / sm.ph / sm.dz2 are then the next row's
+        qh_grad_row(G, sm, a, tgt, inv, xi, P, t, [&](float cur, float) { bt.next_actions[b] = a_star; bt.target[b] = tgt; bt.current[b] = cur; });
     }
-    // ---- the workgroup's slab ----
-    float* const slab = slabs + (size_t)blockIdx.x * DD_STRIDE;
-    if (t < 2 * DD_H2) slab[DD_W3 + t] = g3;
-    else if (t < 2 * DD_H2 + 2) slab[DD_B3 + t - 2 * DD_H2] = gb3;
-    ts_store(g, slab, t);
-    if (t == 0) { slab[DD_NP] = loss; slab[DD_NP + 1] = 0.0f; }
+    qh_store(G, slabs + (size_t)blockIdx.x * QH_STRIDE, t);
 }
 
 __global__ void __launch_bounds__(32 * RG_RED_GROUPS) ddqn_reduce_kernel(const float* __restrict__ slabs, int n_slabs, float inv, float* __restrict__ grads,
                                                                           float* __restrict__ loss, float* __restrict__ p, float* __restrict__ m, float* __restrict__ v,
                                                                           rg_adam_consts k, int adam) {
-    rg_reduce<DD_NP, DD_STRIDE>(slabs, n_slabs, inv, grads, loss, p, m, v, k, adam);
+    rg_reduce<QH_NP, QH_STRIDE>(slabs, n_slabs, inv, grads, loss, p, m, v, k, adam);
 }
 
 // ---- C ABI -------------------------------------------------------------------------------------------
@@ -290,7 +203,7 @@ static int dd_grad(const mi_ddqn_ring_t* ring, const mi_ddqn_batch_t* b, const m
     int rc = rg_check_batch(ring, b, INT_MAX, "batch <= 0", [](const mi_ddqn_batch_t& bt) { return bt.current && bt.target; });
     if (rc == RG_OK && update) rc = rg_check_opt(opt);
     if (rc != RG_OK) return rc;
-    return rg_launch_grad<DD_NP>(ddqn_grad_kernel, ddqn_reduce_kernel, ring, b, dd_slabs(b->batch), 1.0f / (float)b->batch, update ? opt : nullptr, s);
+    return rg_launch_grad<QH_NP>(ddqn_grad_kernel, ddqn_reduce_kernel, ring, b, dd_slabs(b->batch), 1.0f / (float)b->batch, update ? opt : nullptr, s);
 }
 extern "C" int mi_ddqn_grad(const mi_ddqn_ring_t* ring, const mi_ddqn_batch_t* b, void* stream) { return dd_grad(ring, b, nullptr, false, (hipStream_t)stream); }
 extern "C" int mi_ddqn_update(const mi_ddqn_ring_t* ring, const mi_ddqn_batch_t* b, const mi_ddqn_adam_t* opt, void* stream) {

@@ -10,9 +10,11 @@ import tempfile
 
 import pytest
 
+import _libsrc as S
+
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 CSRC = os.path.join(ROOT, "deep_rl_amd", "csrc")
-C51_ALLSRC = ["mi_c51.hip", "mi_common.h", "mi_ring.h", "mi_torso.h", "../../include/mi_c51.h", "../../include/mi_rl.h"]
+C51_ALLSRC = S.ALLSRC["_native_c51"]
 
 
 @pytest.fixture(scope="module")
@@ -169,7 +171,7 @@ def test_the_other_libraries_are_still_the_profiled_ones(K):
         out = subprocess.run([sys.executable, os.path.join(CSRC, "srcid.py")] + files, cwd=CSRC, capture_output=True, text=True, timeout=60)
         return out.stdout.strip()
 
-    assert srcid(["mi_reinforce.hip", "mi_common.h", "../../include/mi_reinforce.h", "../../include/mi_rl.h"]) == PG.source_id()
+    assert srcid(S.ALLSRC["_native_pg"]) == PG.source_id()
     bench = os.path.join(ROOT, "profiles", "reinforce_bench.json")
     if os.path.exists(bench):
         assert PG.source_id() in open(bench).read()

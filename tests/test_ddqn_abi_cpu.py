@@ -10,9 +10,11 @@ import tempfile
 
 import pytest
 
+import _libsrc as S
+
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 CSRC = os.path.join(ROOT, "deep_rl_amd", "csrc")
-DDQN_ALLSRC = ["mi_ddqn.hip", "mi_common.h", "mi_ring.h", "mi_torso.h", "../../include/mi_ddqn.h", "../../include/mi_rl.h"]
+DDQN_ALLSRC = S.ALLSRC["_native_ddqn"]
 
 
 @pytest.fixture(scope="module")
@@ -182,11 +184,10 @@ def test_the_other_libraries_are_still_the_profiled_ones(K):
         out = subprocess.run([sys.executable, os.path.join(CSRC, "srcid.py")] + files, cwd=CSRC, capture_output=True, text=True, timeout=60)
         return out.stdout.strip()
 
-    inc = "../../include/"
-    assert srcid(["mi_reinforce.hip", "mi_common.h", inc + "mi_reinforce.h", inc + "mi_rl.h"]) == PG.source_id()
-    assert srcid(["mi_c51.hip", "mi_common.h", "mi_ring.h", "mi_torso.h", inc + "mi_c51.h", inc + "mi_rl.h"]) == C5.source_id()
-    assert srcid(["mi_iqn.hip", "mi_common.h", "mi_ring.h", inc + "mi_iqn.h", inc + "mi_rl.h"]) == IQ.source_id()
-    assert srcid(["mi_qr.hip", "mi_common.h", "mi_ring.h", "mi_torso.h", inc + "mi_qr.h", inc + "mi_rl.h"]) == QR.source_id()
+    assert srcid(S.ALLSRC["_native_pg"]) == PG.source_id()
+    assert srcid(S.ALLSRC["_native_c51"]) == C5.source_id()
+    assert srcid(S.ALLSRC["_native_iqn"]) == IQ.source_id()
+    assert srcid(S.ALLSRC["_native_qr"]) == QR.source_id()
     assert PG.source_id() in open(os.path.join(ROOT, "profiles", "reinforce_bench.json")).read()
     assert json.load(open(os.path.join(ROOT, "profiles", "c51_bench.json")))["c51_source_id"] == C5.source_id()
     assert IQ.source_id() in open(os.path.join(ROOT, "profiles", "iqn_bench.json")).read()
@@ -201,6 +202,14 @@ def test_the_other_libraries_are_still_the_profiled_ones(K):
     mk = open(os.path.join(CSRC, "Makefile")).read()
     assert "DDQN_ALLSRC = " + " ".join(DDQN_ALLSRC) in mk and "$(OUT_DDQN)" in mk.split("all:")[1].splitlines()[0] and "$(OUT_DDQN)" in mk.split("clean:")[1]
     assert "-DMI_DDQN_SOURCE_ID" in mk
+    # the table of tests/_libsrc.py is the Makefile's: every entry equals its `X_ALLSRC =` line, and there is no such line without an entry
+    lines = dict(re.findall(r"^(\w*ALLSRC) = (.*)$", mk, re.M))
+    assert set(S.ALLSRC) == set(S.MAKE_VAR) and sorted(S.MAKE_VAR.values()) == sorted(lines) and len(lines) == 12
+    for mod, files in S.ALLSRC.items():
+        assert lines[S.MAKE_VAR[mod]].split() == files, mod
+    assert re.search(r"^SRCS\s*= (.*)$", mk, re.M).group(1).split() == S.SRCS
+    # mi_qhead.h, the plain head, is in the lists of this library and of libmirl_mdqn.so and in no other
+    assert sorted(v for v, line in lines.items() if "mi_qhead.h" in line.split()) == ["DDQN_ALLSRC", "MD_ALLSRC"]
 
 
 def test_engine_surface_is_callable_where_it_must_be():

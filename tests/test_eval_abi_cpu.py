@@ -10,21 +10,22 @@ import tempfile
 
 import pytest
 
+import _libsrc as S
+
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 CSRC = os.path.join(ROOT, "deep_rl_amd", "csrc")
-INC = "../../include/"
-EV_ALLSRC = ["mi_eval.hip", "mi_common.h", "mi_torso.h", INC + "mi_eval.h", INC + "mi_rl.h"]
+EV_ALLSRC = S.ALLSRC["_native_ev"]
 # the ten older libraries: (binding module, the Makefile's source list, the id this feature found and must leave)
 OLDER = (
-    ("_native_pg", ["mi_reinforce.hip", "mi_common.h", INC + "mi_reinforce.h", INC + "mi_rl.h"], "c30878346b6f"),
-    ("_native_c51", ["mi_c51.hip", "mi_common.h", "mi_ring.h", "mi_torso.h", INC + "mi_c51.h", INC + "mi_rl.h"], "976edde66621"),
-    ("_native_iqn", ["mi_iqn.hip", "mi_common.h", "mi_ring.h", INC + "mi_iqn.h", INC + "mi_rl.h"], "e35a43ebf95c"),
-    ("_native_qr", ["mi_qr.hip", "mi_common.h", "mi_ring.h", "mi_torso.h", INC + "mi_qr.h", INC + "mi_rl.h"], "8100cd09ac96"),
-    ("_native_ddqn", ["mi_ddqn.hip", "mi_common.h", "mi_ring.h", "mi_torso.h", INC + "mi_ddqn.h", INC + "mi_rl.h"], "45a0ddad7ca6"),
-    ("_native_pdd", ["mi_pdd.hip", "mi_common.h", "mi_ring.h", "mi_torso.h", "mi_dueling.h", INC + "mi_pdd.h", INC + "mi_rl.h"], "65d24581dff3"),
-    ("_native_ns", ["mi_nstep.hip", "mi_common.h", "mi_ring.h", "mi_torso.h", "mi_nwalk.h", "mi_dueling.h", INC + "mi_nstep.h", INC + "mi_rl.h"], "ffb74331a9c8"),
-    ("_native_nz", ["mi_noisy.hip", "mi_common.h", "mi_ring.h", "mi_torso.h", "mi_nwalk.h", "mi_dueling.h", INC + "mi_noisy.h", INC + "mi_rl.h"], "74e65f9c5f40"),
-    ("_native_rb", ["mi_rainbow.hip", "mi_common.h", "mi_ring.h", "mi_torso.h", "mi_nwalk.h", INC + "mi_rainbow.h", INC + "mi_rl.h"], "47a9b95b193c"),
+    ("_native_pg", S.ALLSRC["_native_pg"], "c30878346b6f"),
+    ("_native_c51", S.ALLSRC["_native_c51"], "976edde66621"),
+    ("_native_iqn", S.ALLSRC["_native_iqn"], "e35a43ebf95c"),
+    ("_native_qr", S.ALLSRC["_native_qr"], "8100cd09ac96"),
+    ("_native_ddqn", S.ALLSRC["_native_ddqn"], "08f332993a59"),
+    ("_native_pdd", S.ALLSRC["_native_pdd"], "65d24581dff3"),
+    ("_native_ns", S.ALLSRC["_native_ns"], "ffb74331a9c8"),
+    ("_native_nz", S.ALLSRC["_native_nz"], "74e65f9c5f40"),
+    ("_native_rb", S.ALLSRC["_native_rb"], "47a9b95b193c"),
 )
 LIBMIRL_ID = "6106efad96ba"
 

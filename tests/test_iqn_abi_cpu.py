@@ -10,14 +10,16 @@ import tempfile
 
 import pytest
 
+import _libsrc as S
+
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 CSRC = os.path.join(ROOT, "deep_rl_amd", "csrc")
-IQN_ALLSRC = ["mi_iqn.hip", "mi_common.h", "mi_ring.h", "../../include/mi_iqn.h", "../../include/mi_rl.h"]
+IQN_ALLSRC = S.ALLSRC["_native_iqn"]
 # the three other lists, as the Makefile states them (C51's holds mi_torso.h, the torso it shares with QR-DQN and Double DQN; IQN's does not)
 OTHER_ALLSRC = {
-    "ALLSRC": "$(SRCS) mi_common.h mi_grad_kernel.inc mi_sac_rowgroup.inc ../../include/mi_rl.h",
-    "PG_ALLSRC": "mi_reinforce.hip mi_common.h ../../include/mi_reinforce.h ../../include/mi_rl.h",
-    "C51_ALLSRC": "mi_c51.hip mi_common.h mi_ring.h mi_torso.h ../../include/mi_c51.h ../../include/mi_rl.h",
+    "ALLSRC": " ".join(S.ALLSRC["_native"]),
+    "PG_ALLSRC": " ".join(S.ALLSRC["_native_pg"]),
+    "C51_ALLSRC": " ".join(S.ALLSRC["_native_c51"]),
 }
 
 

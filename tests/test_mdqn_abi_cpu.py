@@ -11,9 +11,11 @@ import tempfile
 
 import pytest
 
+import _libsrc as S
+
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 CSRC = os.path.join(ROOT, "deep_rl_amd", "csrc")
-MD_ALLSRC = ["mi_mdqn.hip", "mi_common.h", "mi_ring.h", "mi_torso.h", "../../include/mi_mdqn.h", "../../include/mi_rl.h"]
+MD_ALLSRC = S.ALLSRC["_native_md"]
 
 
 @pytest.fixture(scope="module")
@@ -223,12 +225,11 @@ def test_the_other_libraries_are_still_what_their_sources_give(K):
         out = subprocess.run([sys.executable, os.path.join(CSRC, "srcid.py")] + files, cwd=CSRC, capture_output=True, text=True, timeout=60)
         return out.stdout.strip()
 
-    inc = "../../include/"
     assert json.load(open(os.path.join(ROOT, "profiles", "latest_pmc.json"))).get("source_id") == N.lib().mi_source_id().decode()
-    assert srcid(["mi_ddqn.hip", "mi_common.h", "mi_ring.h", "mi_torso.h", inc + "mi_ddqn.h", inc + "mi_rl.h"]) == DQ.source_id()
+    assert srcid(S.ALLSRC["_native_ddqn"]) == DQ.source_id()
     assert json.load(open(os.path.join(ROOT, "profiles", "ddqn_bench.json")))["ddqn_source_id"] == DQ.source_id()
-    assert srcid(["mi_pdd.hip", "mi_common.h", "mi_ring.h", "mi_torso.h", "mi_dueling.h", inc + "mi_pdd.h", inc + "mi_rl.h"]) == PD.source_id()
-    assert srcid(["mi_nstep.hip", "mi_common.h", "mi_ring.h", "mi_torso.h", "mi_nwalk.h", "mi_dueling.h", inc + "mi_nstep.h", inc + "mi_rl.h"]) == NS.source_id()
+    assert srcid(S.ALLSRC["_native_pdd"]) == PD.source_id()
+    assert srcid(S.ALLSRC["_native_ns"]) == NS.source_id()
     assert srcid(MD_ALLSRC) == K.source_id()
     bench = os.path.join(ROOT, "profiles", "mdqn_bench.json")
     if os.path.exists(bench):
@@ -237,6 +238,8 @@ def test_the_other_libraries_are_still_what_their_sources_give(K):
     mk = open(os.path.join(CSRC, "Makefile")).read()
     assert "MD_ALLSRC = " + " ".join(MD_ALLSRC) in mk and "$(OUT_MD)" in mk.split("all:")[1].splitlines()[0] and "$(OUT_MD)" in mk.split("clean:")[1]
     assert "-DMI_MD_SOURCE_ID" in mk and "OUT_MD ?= ../libmirl_mdqn.so" in mk
+    # mi_qhead.h, the plain head, is in the lists of this library and of libmirl_ddqn.so and in no other
+    assert sorted(v for v, line in re.findall(r"^(\w*ALLSRC) = (.*)$", mk, re.M) if "mi_qhead.h" in line.split()) == ["DDQN_ALLSRC", "MD_ALLSRC"]
     assert "_native_md.lib().mi_md_version() == _native_md.ABI_VERSION" in open(os.path.join(ROOT, "__graft_entry__.py")).read()
 
 

@@ -10,9 +10,11 @@ import tempfile
 
 import pytest
 
+import _libsrc as S
+
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 CSRC = os.path.join(ROOT, "deep_rl_amd", "csrc")
-NZ_ALLSRC = ["mi_noisy.hip", "mi_common.h", "mi_ring.h", "mi_torso.h", "mi_nwalk.h", "mi_dueling.h", "../../include/mi_noisy.h", "../../include/mi_rl.h"]
+NZ_ALLSRC = S.ALLSRC["_native_nz"]
 ENTRY = ("version", "last_error", "source_id", "workspace_bytes", "noise", "forward", "act_steps", "target", "grad", "update")
 
 
@@ -269,7 +271,7 @@ def test_the_other_libraries_are_still_what_their_sources_give(K):
     allsrc = lambda var: re.search(r"^%s = (.*)$" % var, mk, flags=re.M).group(1).split()   # noqa: E731
     older = (("ALLSRC", N.lib().mi_source_id().decode()), ("PG_ALLSRC", PG.source_id()), ("C51_ALLSRC", C5.source_id()), ("IQN_ALLSRC", IQ.source_id()),
              ("QR_ALLSRC", QR.source_id()), ("DDQN_ALLSRC", DQ.source_id()), ("PDD_ALLSRC", PD.source_id()), ("NS_ALLSRC", NS.source_id()))
-    srcs = "mi_env.hip mi_rollout.hip mi_update.hip mi_dqn.hip mi_sac.hip mi_comm.hip".split()
+    srcs = S.SRCS
     for var, sid in older:
         files = allsrc(var)
         assert "mi_noisy.hip" not in files and "../../include/mi_noisy.h" not in files

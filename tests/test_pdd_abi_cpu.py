@@ -9,9 +9,11 @@ import tempfile
 
 import pytest
 
+import _libsrc as S
+
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 CSRC = os.path.join(ROOT, "deep_rl_amd", "csrc")
-PDD_ALLSRC = ["mi_pdd.hip", "mi_common.h", "mi_ring.h", "mi_torso.h", "mi_dueling.h", "../../include/mi_pdd.h", "../../include/mi_rl.h"]
+PDD_ALLSRC = S.ALLSRC["_native_pdd"]
 
 
 @pytest.fixture(scope="module")
@@ -219,8 +221,7 @@ def test_the_other_libraries_are_still_what_their_sources_give(K):
         out = subprocess.run([sys.executable, os.path.join(CSRC, "srcid.py")] + files, cwd=CSRC, capture_output=True, text=True, timeout=60)
         return out.stdout.strip()
 
-    inc = "../../include/"
-    assert srcid(["mi_ddqn.hip", "mi_common.h", "mi_ring.h", "mi_torso.h", inc + "mi_ddqn.h", inc + "mi_rl.h"]) == DQ.source_id()
+    assert srcid(S.ALLSRC["_native_ddqn"]) == DQ.source_id()
     assert json.load(open(os.path.join(ROOT, "profiles", "ddqn_bench.json")))["ddqn_source_id"] == DQ.source_id()      # mi_ring.h / mi_torso.h / mi_common.h did not move
     assert srcid(PDD_ALLSRC) == K.source_id()
     bench = os.path.join(ROOT, "profiles", "pdd_bench.json")

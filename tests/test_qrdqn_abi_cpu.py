@@ -10,9 +10,11 @@ import tempfile
 
 import pytest
 
+import _libsrc as S
+
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 CSRC = os.path.join(ROOT, "deep_rl_amd", "csrc")
-QR_ALLSRC = ["mi_qr.hip", "mi_common.h", "mi_ring.h", "mi_torso.h", "../../include/mi_qr.h", "../../include/mi_rl.h"]
+QR_ALLSRC = S.ALLSRC["_native_qr"]
 
 
 @pytest.fixture(scope="module")
@@ -177,10 +179,9 @@ def test_the_other_libraries_are_still_the_profiled_ones(K):
         out = subprocess.run([sys.executable, os.path.join(CSRC, "srcid.py")] + files, cwd=CSRC, capture_output=True, text=True, timeout=60)
         return out.stdout.strip()
 
-    inc = "../../include/"
-    assert srcid(["mi_reinforce.hip", "mi_common.h", inc + "mi_reinforce.h", inc + "mi_rl.h"]) == PG.source_id()
-    assert srcid(["mi_c51.hip", "mi_common.h", "mi_ring.h", "mi_torso.h", inc + "mi_c51.h", inc + "mi_rl.h"]) == C5.source_id()
-    assert srcid(["mi_iqn.hip", "mi_common.h", "mi_ring.h", inc + "mi_iqn.h", inc + "mi_rl.h"]) == IQ.source_id()
+    assert srcid(S.ALLSRC["_native_pg"]) == PG.source_id()
+    assert srcid(S.ALLSRC["_native_c51"]) == C5.source_id()
+    assert srcid(S.ALLSRC["_native_iqn"]) == IQ.source_id()
     assert PG.source_id() in open(os.path.join(ROOT, "profiles", "reinforce_bench.json")).read()
     assert json.load(open(os.path.join(ROOT, "profiles", "c51_bench.json")))["c51_source_id"] == C5.source_id()
     assert IQ.source_id() in open(os.path.join(ROOT, "profiles", "iqn_bench.json")).read()

@@ -10,6 +10,8 @@ import tempfile
 
 import pytest
 
+import _libsrc as S
+
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 CSRC = os.path.join(ROOT, "deep_rl_amd", "csrc")
 
@@ -151,6 +153,6 @@ def test_first_library_is_still_the_profiled_one(PG):
     rec = json.load(open(os.path.join(ROOT, "profiles", "latest_pmc.json")))
     assert rec.get("source_id") == mine
     assert PG.source_id() != mine
-    out = subprocess.run([sys.executable, os.path.join(CSRC, "srcid.py"), "mi_reinforce.hip", "mi_common.h", "../../include/mi_reinforce.h", "../../include/mi_rl.h"],
+    out = subprocess.run([sys.executable, os.path.join(CSRC, "srcid.py")] + S.ALLSRC["_native_pg"],
                          cwd=CSRC, capture_output=True, text=True, timeout=60)
     assert out.stdout.strip() == PG.source_id()

@@ -1,17 +1,17 @@
 #!/usr/bin/env python3
-"""The seeded byte-for-byte sequence of a ring-replay library (C51, IQN, QR-DQN, Double DQN, prioritized dueling Double DQN and its n-step and noisy forms): what a
-refactor of mi_ring.h / mi_torso.h / mi_dueling.h / mi_*.hip must leave unchanged.
+"""The seeded byte-for-byte sequence of a ring-replay library (C51, IQN, QR-DQN, Double DQN, Munchausen DQN, prioritized dueling Double DQN and its n-step and noisy
+forms): what a refactor of mi_ring.h / mi_torso.h / mi_dueling.h / mi_qhead.h / mi_*.hip must leave unchanged.
 
-    tools/ring_ab_hashes.py --algo c51|iqn|qrdqn|ddqn|pdd|nstep|noisy --envs N --slots S --batch B --out FILE   [--prioritized 0|1] [--n-step N] [--noisy 0|1]
+    tools/ring_ab_hashes.py --algo c51|iqn|qrdqn|ddqn|mdqn|pdd|nstep|noisy --envs N --slots S --batch B --out FILE   [--prioritized 0|1] [--n-step N] [--noisy 0|1]
 
-One process, one library set (the ones ``MIRL_C51_SO`` / ``MIRL_IQN_SO`` / ``MIRL_QR_SO`` / ``MIRL_DDQN_SO`` / ``MIRL_PDD_SO`` / ``MIRL_NS_SO`` / ``MIRL_NZ_SO``
-name, else the built ones; the n-step and the noisy engine act through libmirl_pdd.so), no retry.  It runs
+One process, one library set (the ones ``MIRL_C51_SO`` / ``MIRL_IQN_SO`` / ``MIRL_QR_SO`` / ``MIRL_DDQN_SO`` / ``MIRL_MDQN_SO`` / ``MIRL_PDD_SO`` / ``MIRL_NS_SO`` /
+``MIRL_NZ_SO`` name, else the built ones; the n-step and the noisy engine act through libmirl_pdd.so, the Munchausen engine through libmirl_ddqn.so), no retry.  It runs
   1 reset   2 act(64)   3 act(7) with forced actions and resets (IQN: forced taus and taus_out too)   4 six train_step()s with deep_rl_amd.Adam
   5 sample(indices) + target() + grad() + optimizer.step   6 sync_target   7 act(64) at the epsilon floor
 and after every stage writes the sha256 of the raw bytes of every tensor: the ring, the env's fp64 state and TimeLimit counters, the carried observation,
 episode_stats, the drained episodes, batch_inds, next_actions, the target and current tensors, the taus, grads, loss, both parameter vectors and Adam's moments;
-for pdd / nstep / noisy also td_abs, the n-step horizon and, prioritized, weights, priorities and max_priority.  Stage 3 is forced for every algorithm but nstep,
-which has no acting kernel of its own.  ``--noisy 0`` runs the mean network under the epsilon schedule, ``--noisy 1`` the noise with epsilon 0.
+for pdd / nstep / noisy also td_abs, the n-step horizon and, prioritized, weights, priorities and max_priority; for mdqn also bonus and soft_value (alpha 0.9, tau 0.03,
+clip -1).  Stage 3 is forced for every algorithm but nstep and mdqn, which have no acting kernel of their own.  ``--noisy 0`` runs the mean network under the epsilon schedule, ``--noisy 1`` the noise with epsilon 0.
 FILE holds nothing but the stages (no library id, no time), so two runs are compared with ``cmp``; the library's id goes to stdout.
 The schedule puts stage 2 on the decaying epsilon (Double DQN and IQN: its first 16 steps before learning_starts) and stage 7 on the floor.
 """
@@ -60,6 +60,8 @@ def make(algo, n, slots, batch, seed, prioritized=True, n_step=3, noisy=True):
         "c51": (D.C51QNetwork, D.C51Engine, "_native_c51", ("probs", "target_probs"), {}),
         "qrdqn": (D.QRQNetwork, D.QRDQNEngine, "_native_qr", ("current", "target_quantiles"), {}),
         "ddqn": (D.QNetwork, D.DoubleDQNEngine, "_native_ddqn", ("current", "target_values"), {"learning_starts": LEARNING_STARTS}),
+        "mdqn": (D.QNetwork, D.MunchausenDQNEngine, "_native_md", ("current", "target_values", "bonus", "soft_value"),
+                 {"learning_starts": LEARNING_STARTS, "alpha": 0.9, "tau": 0.03, "clip_lo": -1.0}),
     }[algo]
     q = net(env); t = net(env); t.load_state_dict(q.state_dict())
     eng = engine(env, q, t, D.Adam(q, lr=2.5e-4, eps=0.01 / batch), slots=slots, batch_size=batch, total_timesteps=2 * DECAY_STEPS, exploration_fraction=0.5,
@@ -86,7 +88,7 @@ def snapshot(eng, own, extra):
 
 def main():
     ap = argparse.ArgumentParser()
-    ap.add_argument("--algo", required=True, choices=("c51", "iqn", "qrdqn", "ddqn", "pdd", "nstep", "noisy"))
+    ap.add_argument("--algo", required=True, choices=("c51", "iqn", "qrdqn", "ddqn", "mdqn", "pdd", "nstep", "noisy"))
     ap.add_argument("--envs", type=int, required=True)
     ap.add_argument("--slots", type=int, required=True)
     ap.add_argument("--batch", type=int, required=True)
@@ -113,7 +115,7 @@ def main():
     if iqn:
         forced["forced_taus"] = torch.rand((7, n, K.N_QUANT), generator=gen, dtype=torch.float32)
         forced["taus_out"] = extra["taus_out"] = torch.zeros((7, n, K.N_QUANT), dtype=torch.float32, device=eng.device)
-    if args.algo == "nstep":   # its acting is libmirl_pdd.so's: --algo pdd covers the forced launch
+    if args.algo in ("nstep", "mdqn"):   # their acting is libmirl_pdd.so's / libmirl_ddqn.so's: --algo pdd / ddqn covers the forced launch
         forced = {}
     eng.act(7, **forced); stage("3 act(7) forced")
     for _ in range(6):
