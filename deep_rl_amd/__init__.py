@@ -11,7 +11,7 @@ from ._native import set_contraction, get_contraction  # noqa: F401
 from .envs import make, CartPoleVecEnv, PendulumVecEnv  # noqa: F401
 from .agent import ActorCritic, QNetwork, DuelingQNetwork, SoftQNetwork, Actor, DropoutPolicy, C51QNetwork, QRQNetwork, layer_init, pack  # noqa: F401
 from .agent import FeaturesExtractor, CosineEmbeddingNetwork, QuantileNetwork, iqn_forward  # noqa: F401
-from .agent import NoisyLinear, NoisyDuelingQNetwork, RainbowQNetwork  # noqa: F401
+from .agent import NoisyLinear, NoisyDuelingQNetwork, RainbowQNetwork, LinearPolicy  # noqa: F401
 from .optim import ClipAdam, Adam  # noqa: F401
 from .engine import PPOEngine  # noqa: F401
 from .dqn_engine import DQNEngine, DuelingDQNEngine, PERDQNEngine  # noqa: F401
@@ -26,6 +26,7 @@ from .pdd_engine import PDDDQNEngine  # noqa: F401  (libmirl_pdd.so itself loads
 from .nstep_engine import NStepDQNEngine  # noqa: F401  (libmirl_nstep.so itself loads on first use)
 from .noisy_engine import NoisyDQNEngine  # noqa: F401  (libmirl_noisy.so itself loads on first use)
 from .rainbow_engine import RainbowEngine  # noqa: F401  (libmirl_rainbow.so itself loads on first use)
+from .ars_engine import ARSEngine  # noqa: F401  (libmirl_ars.so itself loads on first use)
 
 
 def __getattr__(name):
@@ -39,4 +40,4 @@ def __getattr__(name):
 
 
 __all__ = ["make", "CartPoleVecEnv", "ActorCritic", "QNetwork", "layer_init", "ClipAdam", "PPOEngine", "DQNEngine",
-           "DuelingQNetwork", "DuelingDQNEngine", "PERDQNEngine", "PendulumVecEnv", "SoftQNetwork", "Actor", "Adam", "SACEngine", "DropoutPolicy", "ReinforceEngine", "C51QNetwork", "C51Engine", "FeaturesExtractor", "CosineEmbeddingNetwork", "QuantileNetwork", "iqn_forward", "IQNEngine", "QRQNetwork", "QRDQNEngine", "DoubleDQNEngine", "MunchausenDQNEngine", "PDDDQNEngine", "NStepDQNEngine", "NoisyLinear", "NoisyDuelingQNetwork", "NoisyDQNEngine", "RainbowQNetwork", "RainbowEngine", "pack", "set_contraction", "get_contraction", "evaluate", "EvalResult"]
+           "DuelingQNetwork", "DuelingDQNEngine", "PERDQNEngine", "PendulumVecEnv", "SoftQNetwork", "Actor", "Adam", "SACEngine", "DropoutPolicy", "ReinforceEngine", "C51QNetwork", "C51Engine", "FeaturesExtractor", "CosineEmbeddingNetwork", "QuantileNetwork", "iqn_forward", "IQNEngine", "QRQNetwork", "QRDQNEngine", "DoubleDQNEngine", "MunchausenDQNEngine", "PDDDQNEngine", "NStepDQNEngine", "NoisyLinear", "NoisyDuelingQNetwork", "NoisyDQNEngine", "RainbowQNetwork", "RainbowEngine", "LinearPolicy", "ARSEngine", "pack", "set_contraction", "get_contraction", "evaluate", "EvalResult"]

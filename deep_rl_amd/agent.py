@@ -524,3 +524,13 @@ class RainbowQNetwork(_FlatModule):
     def forward(self, observation):
         atoms = torch.linspace(self.v_min, self.v_max, self.n_atoms)
         return (self.get_probs(observation) * atoms).sum(-1)
+
+
+class LinearPolicy(_FlatModule):
+    """The policy of Augmented Random Search (include/mi_ars.h): M, f32 [n_actions][4] without a bias, over one flat fp32 device buffer of 8 floats; it starts at
+    zero, as the paper's does.  The action of an observation is argmax_a (M x)_a with x the normalised observation — ARSEngine holds the normaliser."""
+
+    def __init__(self, env, device=None):
+        super().__init__()
+        self.weight = nn.Parameter(torch.zeros(env.action_space.n, int(np.prod(env.observation_space.shape))), requires_grad=False)
+        self._finish(env, device, 8)

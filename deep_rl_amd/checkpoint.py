@@ -22,6 +22,7 @@ from .dqn_engine import DQNEngine, DuelingDQNEngine, PERDQNEngine
 from .engine import PPOEngine
 from .reinforce_engine import ReinforceEngine
 from .sac_engine import SACEngine
+from .ars_engine import ARSEngine
 
 FORMAT = 1
 
@@ -61,6 +62,10 @@ def _has_priorities(engine):
 
 def state_dict(engine, include_replay=True):
     """-> {name: array}: everything needed to continue `engine` exactly."""
+    if isinstance(engine, ARSEngine):   # no env, no ring, no optimizer: the policy, the observation statistics, the normaliser and the iteration the draws are keyed by
+        st = {"format": np.int64(FORMAT), "kind": type(engine).__name__, "n_directions": np.int64(engine.n_directions), "seed": np.int64(engine.seed),
+              "env_id_base": np.int64(engine.env_id_base), "params": engine.policy.flat, "stats": engine.stats, "norm": engine.norm, "iteration": engine.iteration}
+        return {k: (v.detach().cpu().numpy() if torch.is_tensor(v) else np.asarray(v)) for k, v in st.items()}
     env = engine.env
     st = {"format": np.int64(FORMAT), "kind": type(engine).__name__, "num_envs": np.int64(env.num_envs), "seed": np.int64(env._seed),
           "env_id_base": np.int64(env.env_id_base), "env_blob": _env_blob(env), "observation": engine.observation}
@@ -100,7 +105,7 @@ def _npz_path(path):
 
 def save(path, engine, include_replay=True):
     """Write `engine` to ``path`` ('.npz' is appended when missing, as np.savez does).  -> the path written."""
-    if engine.observation is None:
+    if not isinstance(engine, ARSEngine) and engine.observation is None:
         raise N.MiError("checkpoint: the engine was never reset (no carried-over observation to save)")
     torch.cuda.current_stream(engine.device).synchronize()
     path = _npz_path(path)
@@ -114,10 +119,24 @@ def _check_shape(z, name, want):
         raise N.MiError("checkpoint: %s has shape %s, this engine needs %s" % (name, tuple(z[name].shape), tuple(want)))
 
 
+def _load_ars(z, engine):
+    if "format" not in z or int(z["format"]) != FORMAT:
+        raise N.MiError("checkpoint: format %s, this build reads format %d" % (z.get("format"), FORMAT))
+    if str(z["kind"]) != "ARSEngine" or int(z["n_directions"]) != engine.n_directions or int(z["seed"]) != engine.seed or int(z["env_id_base"]) != engine.env_id_base:
+        raise N.MiError("checkpoint: written for %s with (n_directions, seed, env_id_base) = (%s, %s, %s); this engine is ARSEngine (%d, %d, %d)" % (
+            z["kind"], z.get("n_directions"), z["seed"], z["env_id_base"], engine.n_directions, engine.seed, engine.env_id_base))
+    for name, own in (("params", engine.policy.flat), ("stats", engine.stats), ("norm", engine.norm), ("iteration", engine.iteration)):
+        _check_shape(z, name, own.shape)
+        own.copy_(torch.from_numpy(z[name]).to(engine.device))
+    return engine
+
+
 def load(path, engine):
     """Restore `engine` (built with the same sizes, seed and env_id_base) from a checkpoint written by save()."""
     with np.load(_npz_path(path), allow_pickle=False) as zf:
         z = {k: zf[k] for k in zf.files}
+    if isinstance(engine, ARSEngine):
+        return _load_ars(z, engine)
     env = engine.env
     if "format" not in z or int(z["format"]) != FORMAT:
         raise N.MiError("checkpoint: format %s, this build reads format %d" % (z.get("format"), FORMAT))
